@@ -9,7 +9,12 @@
 # (engine.py:645-649).  Synthetic data (no network), random-init weights,
 # fp32 (the reference's compute dtype; bf16 is §8 f4).
 #
-#   python bench.py --gpus N --steps K --warmup W
+#   python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+#
+# A plain run sets up, warms up, times the K steps and prints the result
+# line.  --full adds the legs that take runs of their own (in-step kernel
+# profile + roofline, CPU baseline).  --dump-outputs writes what the last
+# timed step left behind (losses, updated params, AdamW first moments).
 #
 # N>1 is launched by the driver via torch.distributed.run (one rank/GPU,
 # RCCL).  Topology: N=1 -> 1 stage; N=2 -> 2 stages; N=4 -> 4 stages;
@@ -231,6 +236,50 @@ def measure_roofline(args, device):
     }
 
 
+DUMP_BUDGET_BYTES = 16 << 20  # all dumped arrays together (cap: 64 MB)
+
+
+def _dump_sample(t, k):
+    """float32 host copy of `t`, or of a fixed seeded sample of k of its
+    elements (sorted indices; the same for every run and every build)."""
+    t = t.detach().reshape(-1)
+    if t.numel() > k:
+        g = torch.Generator().manual_seed(t.numel())
+        idx = torch.randint(0, t.numel(), (k,), generator=g).sort().values
+        t = t[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(out_dir, my_pipeline):
+    """Write what the timed path produced in its last step as
+    <out_dir>/<name>.npy (float32): the loss buffers the last stage holds
+    (one per pipe slot, i.e. the last microbatches of the step, plus the
+    running total) and, per layer of this rank, the updated fp32 master
+    params and AdamW first moments — sampled so everything fits the
+    budget.  Replicas hold identical state, so only pipeline 0 writes."""
+    import numpy as np
+    if my_pipeline._pipeline_id != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    ex = my_pipeline.execution
+    if my_pipeline.is_last_stage():
+        slots = sorted(ex._loss_bufs)
+        np.save(os.path.join(out_dir, "loss_last_microbatches.npy"),
+                np.concatenate([_dump_sample(ex._loss_bufs[s], 1 << 30)
+                                for s in slots]))
+        np.save(os.path.join(out_dir, "total_loss.npy"),
+                _dump_sample(ex.total_loss, 1 << 30))
+    n_layers = my_pipeline.model_cfg.n_layers_total
+    k = DUMP_BUDGET_BYTES // (4 * 2 * n_layers)
+    opt = ex._optimizer
+    for layer, m in zip(opt.layers, opt._m):
+        np.save(os.path.join(out_dir, f"param_layer{layer.layer_id:02d}.npy"),
+                _dump_sample(layer.flat_param, k))
+        np.save(os.path.join(out_dir, f"adam_m_layer{layer.layer_id:02d}.npy"),
+                _dump_sample(m, k))
+
+
 def measure_cpu_baseline():
     """The oracle (CPU restatement of the reference's arithmetic) timed on
     this box's host cores — the reported baseline (kind=port).  Per
@@ -285,8 +334,17 @@ def main():
                          "fp32 masters/grads — north_star's 'MFMA-bf16 "
                          "roofline' target dtype; f32 = the reference's "
                          "own compute dtype, kept as the parity anchor)")
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
-    ap.add_argument("--skip-roofline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step "
+                         "computed (losses, sampled params and AdamW "
+                         "moments) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: "
+                         "in-step kernel profile + roofline, CPU baseline")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave out the CPU-baseline leg")
+    ap.add_argument("--skip-roofline", action="store_true",
+                    help="with --full: leave out the profile/roofline leg")
     ap.add_argument("--probe", choices=["gemm"], default=None,
                     help="run ONLY the dominant-kernel roofline probe "
                          "(for clean rocprofv3 kernel-trace/PMC capture)")
@@ -329,10 +387,16 @@ def main():
     dist.all_reduce(e, op=dist.ReduceOp.MAX)
     elapsed = float(e.item())
 
+    if args.dump_outputs and my_pipeline is not None:
+        dump_outputs(args.dump_outputs, my_pipeline)
+
+    want_roofline = args.full and not args.skip_roofline
+    want_cpu_baseline = args.full and not args.skip_cpu_baseline
+
     # in-step kernel profile (extra untimed steps, all ranks so the
     # collectives stay in sync; bf16 roofline + step split come from this)
     prof = None
-    if not args.skip_roofline:
+    if want_roofline:
         prof, _ = measure_step_profile(my_pipeline, dp)
 
     if rank == 0:
@@ -363,7 +427,7 @@ def main():
                 "parallelism": f"pp{stages}dp{replicas}",
             },
         }
-        if not args.skip_roofline:
+        if want_roofline:
             # bf16: in-step measurement of the production dispatch; f32
             # keeps the standalone probe (validated against rocprofv3 in
             # round 1: bench 399.8 us vs rocprof 406.4 us avg)
@@ -377,10 +441,10 @@ def main():
                     "family's launch stream, over 2 untimed post-bench "
                     "steps; gemm_dw_side overlaps gemm_dx/flash_bwd on a "
                     "side stream, so families can sum past ms_per_step")
-        if not args.skip_cpu_baseline and world == 1:
+        if want_cpu_baseline and world == 1:
             # contract: the CPU-baseline leg runs on rank 0 at N=1 only
             result["cpu_baseline"] = measure_cpu_baseline()
-        print(json.dumps(result))
+        print(json.dumps(result), flush=True)
     dist.destroy_process_group()
 
 
