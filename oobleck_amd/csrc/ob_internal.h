@@ -91,6 +91,21 @@ int ob_layernorm_bwd_bf16(const void* x, const void* w, const void* mean,
                           const void* rstd, const void* dy, void* dx,
                           void* dw, void* db, int64_t rows, int64_t H,
                           int dx_accum, void* stream);
+// fused tail: ln fwd that also writes the stash copy of x (xcopy null = none)
+int ob_layernorm_fwd_copy_bf16(const void* x, const void* w, const void* b,
+                               void* y, void* xcopy, void* mean, void* rstd,
+                               int64_t rows, int64_t H, float eps,
+                               void* stream);
+// ln bwd with dx = bf16(res + v) (res null = none, may equal dx) and the
+// optional side sums sum_res += colsum(res), sum_dx += colsum(dx)
+int ob_layernorm_bwd_res_bf16(const void* x, const void* w, const void* mean,
+                              const void* rstd, const void* dy,
+                              const void* res, void* dx, void* dw, void* db,
+                              void* sum_res, void* sum_dx, int64_t rows,
+                              int64_t H, void* stream);
+// gelu bwd over [M,N] that also accumulates db[N] += colsum(du)
+int ob_gelu_bwd_colsum_bf16(const void* u, const void* dg, void* du,
+                            void* db, int64_t M, int64_t N, void* stream);
 int ob_softmax_causal_fwd_bf16(void* scores, int64_t batch, int64_t Sq,
                                float scale, void* stream);
 int ob_softmax_causal_bwd_bf16(const void* P, void* dP, int64_t batch,

@@ -600,12 +600,15 @@ __global__ __launch_bounds__(256) void k_ln_fwd_bf16(
 
 // wave-per-row ln forward (H in [512, 1024]): no block barriers, 16-B
 // loads; row reductions are wave shfl ladders (the block-per-row kernel
-// measured ~4x off the HBM roofline at H=768).
+// measured ~4x off the HBM roofline at H=768).  COPY: the loaded row
+// is also stored verbatim to xcopy (the layer's activation stash), which
+// replaces a separate device-to-device copy of x.
+template <bool COPY>
 __global__ __launch_bounds__(256) void k_ln_fwd_bf16_w(
     const __bf16* __restrict__ x, const float* __restrict__ w,
     const float* __restrict__ b, __bf16* __restrict__ y,
-    float* __restrict__ mean, float* __restrict__ rstd, int64_t rows, int H,
-    float eps, int wrows) {
+    __bf16* __restrict__ xcopy, float* __restrict__ mean,
+    float* __restrict__ rstd, int64_t rows, int H, float eps, int wrows) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int c0 = lane * 8, c1 = (lane + 64) * 8;
   const bool has1 = c1 < H;
@@ -634,6 +637,14 @@ __global__ __launch_bounds__(256) void k_ln_fwd_bf16_w(
     if (has1) {
       xa1 = *reinterpret_cast<const uint4*>(xa + c1);
       xb1 = *reinterpret_cast<const uint4*>(xb + c1);
+    }
+    if (COPY) {
+      *reinterpret_cast<uint4*>(xcopy + rowa * H + c0) = xa0;
+      if (has1) *reinterpret_cast<uint4*>(xcopy + rowa * H + c1) = xa1;
+      if (hb) {
+        *reinterpret_cast<uint4*>(xcopy + rowb * H + c0) = xb0;
+        if (has1) *reinterpret_cast<uint4*>(xcopy + rowb * H + c1) = xb1;
+      }
     }
     float va0[8], va1[8], vb0[8], vb1[8];
     float sa = 0.f, sqa = 0.f, sb = 0.f, sqb = 0.f;
@@ -703,19 +714,48 @@ __global__ __launch_bounds__(256) void k_ln_fwd_bf16_w(
   }
 }
 
+// y = LN(x); when xcopy is non-null (and != x) it also receives a bit-exact
+// copy of x.  x is read before either output row is written, and the kernel
+// pointers are restrict-qualified: xcopy must not overlap y.
+static bool ln_wave_width(int64_t H) {
+  return H >= 512 && H <= 1024 && H % 8 == 0;
+}
+
+extern "C" int ob_layernorm_fwd_copy_bf16(const void* x, const void* w,
+                                          const void* b, void* y, void* xcopy,
+                                          void* mean, void* rstd,
+                                          int64_t rows, int64_t H, float eps,
+                                          void* stream) {
+  if (xcopy == x) xcopy = nullptr;
+  if (ln_wave_width(H)) {
+    const int wrows = 4;
+    const int grid = (int)((rows + 4 * wrows - 1) / (4 * wrows));
+    if (xcopy)
+      k_ln_fwd_bf16_w<true><<<grid, 256, 0, S(stream)>>>(
+          (const __bf16*)x, (const float*)w, (const float*)b, (__bf16*)y,
+          (__bf16*)xcopy, (float*)mean, (float*)rstd, rows, (int)H, eps,
+          wrows);
+    else
+      k_ln_fwd_bf16_w<false><<<grid, 256, 0, S(stream)>>>(
+          (const __bf16*)x, (const float*)w, (const float*)b, (__bf16*)y,
+          nullptr, (float*)mean, (float*)rstd, rows, (int)H, eps, wrows);
+    OB_LAUNCH_CHECK();
+    return 0;
+  }
+  // other widths compose: copy, then the block-per-row kernel
+  if (xcopy)
+    OB_HIP(hipMemcpyAsync(xcopy, x, (size_t)(rows * H) * sizeof(__bf16),
+                          hipMemcpyDeviceToDevice, S(stream)));
+  return ob_layernorm_fwd_bf16(x, w, b, y, mean, rstd, rows, H, eps, stream);
+}
+
 extern "C" int ob_layernorm_fwd_bf16(const void* x, const void* w,
                                      const void* b, void* y, void* mean,
                                      void* rstd, int64_t rows, int64_t H,
                                      float eps, void* stream) {
-  if (H >= 512 && H <= 1024 && H % 8 == 0) {
-    const int wrows = 4;
-    const int grid = (int)((rows + 4 * wrows - 1) / (4 * wrows));
-    k_ln_fwd_bf16_w<<<grid, 256, 0, S(stream)>>>(
-        (const __bf16*)x, (const float*)w, (const float*)b, (__bf16*)y,
-        (float*)mean, (float*)rstd, rows, (int)H, eps, wrows);
-    OB_LAUNCH_CHECK();
-    return 0;
-  }
+  if (ln_wave_width(H))
+    return ob_layernorm_fwd_copy_bf16(x, w, b, y, nullptr, mean, rstd, rows,
+                                      H, eps, stream);
   const int grid = (int)bmin64(rows, 16384);
   k_ln_fwd_bf16<<<grid, 256, 0, S(stream)>>>(
       (const __bf16*)x, (const float*)w, (const float*)b, (__bf16*)y,
@@ -725,154 +765,6 @@ extern "C" int ob_layernorm_fwd_bf16(const void* x, const void* w,
 }
 
 #define BLN_CHUNK 16
-#define BLN_WROWS 8
-// wave-per-row ln backward (H <= 1024): each of the block's 4 waves owns
-// its rows outright -- the row reductions are wave shfl ladders, no LDS
-// and no per-row __syncthreads (the block-per-row kernel serialized two
-// block reductions per row); 16-B vector loads throughout.  dw/db fold
-// lane accumulators -> LDS (once) -> one global atomic per column per
-// block.
-template <bool DX_ACCUM>
-__global__ __launch_bounds__(256) void k_ln_bwd_bf16_w(
-    const __bf16* __restrict__ x, const float* __restrict__ w,
-    const float* __restrict__ mean, const float* __restrict__ rstd,
-    const __bf16* __restrict__ dy, __bf16* __restrict__ dx,
-    float* __restrict__ dw, float* __restrict__ db, int64_t rows, int H) {
-  __shared__ float redw[4][1024];
-  __shared__ float redb[4][1024];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int c0 = lane * 8, c1 = (lane + 64) * 8;
-  const bool has1 = c1 < H;
-  float accw[2][8] = {}, accb[2][8] = {};
-  float wv0[8], wv1[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    wv0[j] = w[c0 + j];
-    wv1[j] = has1 ? w[c1 + j] : 0.f;
-  }
-  const int64_t r0 = (int64_t)blockIdx.x * (4 * BLN_WROWS) + wid;
-  // ROW PAIRS: interleave the two rows' shfl reduction ladders (ILP 4) —
-  // single-row version measured 2.0 TB/s, shuffle-latency-bound
-  for (int i = 0; i < BLN_WROWS; i += 2) {
-    const int64_t rowa = r0 + (int64_t)i * 4;
-    const int64_t rowb = r0 + (int64_t)(i + 1) * 4;
-    if (rowa >= rows) break;
-    const bool hb = rowb < rows;
-    const __bf16* xra = x + rowa * H;
-    const __bf16* dyra = dy + rowa * H;
-    const __bf16* xrb = x + (hb ? rowb : rowa) * H;
-    const __bf16* dyrb = dy + (hb ? rowb : rowa) * H;
-    const float mua = mean[rowa], rsa = rstd[rowa];
-    const float mub = hb ? mean[rowb] : 0.f, rsb = hb ? rstd[rowb] : 0.f;
-    const uint4 xa0 = *reinterpret_cast<const uint4*>(xra + c0);
-    const uint4 ya0 = *reinterpret_cast<const uint4*>(dyra + c0);
-    const uint4 xb0 = *reinterpret_cast<const uint4*>(xrb + c0);
-    const uint4 yb0 = *reinterpret_cast<const uint4*>(dyrb + c0);
-    uint4 xa1 = {}, ya1 = {}, xb1 = {}, yb1 = {};
-    if (has1) {
-      xa1 = *reinterpret_cast<const uint4*>(xra + c1);
-      ya1 = *reinterpret_cast<const uint4*>(dyra + c1);
-      xb1 = *reinterpret_cast<const uint4*>(xrb + c1);
-      yb1 = *reinterpret_cast<const uint4*>(dyrb + c1);
-    }
-    float s1a = 0.f, s2a = 0.f, s1b = 0.f, s2b = 0.f;
-    float xha0[8], dya0[8], xha1[8], dya1[8];
-    float xhb0[8], dyb0[8], xhb1[8], dyb1[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      xha0[j] = (bf2f(bf_extract(xa0, j)) - mua) * rsa;
-      dya0[j] = bf2f(bf_extract(ya0, j));
-      xhb0[j] = (bf2f(bf_extract(xb0, j)) - mub) * rsb;
-      dyb0[j] = bf2f(bf_extract(yb0, j));
-      s1a += dya0[j] * wv0[j] * xha0[j];
-      s2a += dya0[j] * wv0[j];
-      s1b += dyb0[j] * wv0[j] * xhb0[j];
-      s2b += dyb0[j] * wv0[j];
-      accw[0][j] += dya0[j] * xha0[j];
-      accb[0][j] += dya0[j];
-      if (hb) {
-        accw[0][j] += dyb0[j] * xhb0[j];
-        accb[0][j] += dyb0[j];
-      }
-    }
-    if (has1) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        xha1[j] = (bf2f(bf_extract(xa1, j)) - mua) * rsa;
-        dya1[j] = bf2f(bf_extract(ya1, j));
-        xhb1[j] = (bf2f(bf_extract(xb1, j)) - mub) * rsb;
-        dyb1[j] = bf2f(bf_extract(yb1, j));
-        s1a += dya1[j] * wv1[j] * xha1[j];
-        s2a += dya1[j] * wv1[j];
-        s1b += dyb1[j] * wv1[j] * xhb1[j];
-        s2b += dyb1[j] * wv1[j];
-        accw[1][j] += dya1[j] * xha1[j];
-        accb[1][j] += dya1[j];
-        if (hb) {
-          accw[1][j] += dyb1[j] * xhb1[j];
-          accb[1][j] += dyb1[j];
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      s1a += __shfl_xor(s1a, o, 64);
-      s2a += __shfl_xor(s2a, o, 64);
-      s1b += __shfl_xor(s1b, o, 64);
-      s2b += __shfl_xor(s2b, o, 64);
-    }
-    const float m1a = s1a / H, m2a = s2a / H;
-    const float m1b = s1b / H, m2b = s2b / H;
-    __bf16 oxa[16], oxb[16];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float va = rsa * (dya0[j] * wv0[j] - m2a - xha0[j] * m1a);
-      oxa[j] = (__bf16)(DX_ACCUM ? bf2f(dx[rowa * H + c0 + j]) + va : va);
-      const float vb = rsb * (dyb0[j] * wv0[j] - m2b - xhb0[j] * m1b);
-      oxb[j] =
-          (__bf16)(DX_ACCUM && hb ? bf2f(dx[rowb * H + c0 + j]) + vb : vb);
-    }
-    if (has1) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float va = rsa * (dya1[j] * wv1[j] - m2a - xha1[j] * m1a);
-        oxa[8 + j] =
-            (__bf16)(DX_ACCUM ? bf2f(dx[rowa * H + c1 + j]) + va : va);
-        const float vb = rsb * (dyb1[j] * wv1[j] - m2b - xhb1[j] * m1b);
-        oxb[8 + j] =
-            (__bf16)(DX_ACCUM && hb ? bf2f(dx[rowb * H + c1 + j]) + vb : vb);
-      }
-    }
-    *reinterpret_cast<uint4*>(dx + rowa * H + c0) =
-        *reinterpret_cast<const uint4*>(&oxa[0]);
-    if (has1)
-      *reinterpret_cast<uint4*>(dx + rowa * H + c1) =
-          *reinterpret_cast<const uint4*>(&oxa[8]);
-    if (hb) {
-      *reinterpret_cast<uint4*>(dx + rowb * H + c0) =
-          *reinterpret_cast<const uint4*>(&oxb[0]);
-      if (has1)
-        *reinterpret_cast<uint4*>(dx + rowb * H + c1) =
-            *reinterpret_cast<const uint4*>(&oxb[8]);
-    }
-  }
-  // dw/db: lane accs -> LDS (per wave) -> wave 0 folds -> one atomic/col
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    redw[wid][c0 + j] = accw[0][j];
-    redb[wid][c0 + j] = accb[0][j];
-    if (has1) {
-      redw[wid][c1 + j] = accw[1][j];
-      redb[wid][c1 + j] = accb[1][j];
-    }
-  }
-  __syncthreads();
-  for (int c = threadIdx.x; c < H; c += 256) {
-    atomicAdd(&dw[c], redw[0][c] + redw[1][c] + redw[2][c] + redw[3][c]);
-    atomicAdd(&db[c], redb[0][c] + redb[1][c] + redb[2][c] + redb[3][c]);
-  }
-}
-
 template <bool DX_ACCUM>
 __global__ __launch_bounds__(256) void k_ln_bwd_bf16(
     const __bf16* __restrict__ x, const float* __restrict__ w,
@@ -932,21 +824,10 @@ extern "C" int ob_layernorm_bwd_bf16(const void* x, const void* w,
                                      int dx_accum, void* stream) {
   if (H > 2048) return ob_fail("ln_bwd_bf16: H > 2048 unsupported");
   if (H % 8) return ob_fail("ln_bwd_bf16: H must be a multiple of 8");
-  if (H >= 512 && H <= 1024) {
-    const int grid = (int)((rows + 4 * BLN_WROWS - 1) / (4 * BLN_WROWS));
-    if (dx_accum)
-      k_ln_bwd_bf16_w<true><<<grid, 256, 0, S(stream)>>>(
-          (const __bf16*)x, (const float*)w, (const float*)mean,
-          (const float*)rstd, (const __bf16*)dy, (__bf16*)dx, (float*)dw,
-          (float*)db, rows, (int)H);
-    else
-      k_ln_bwd_bf16_w<false><<<grid, 256, 0, S(stream)>>>(
-          (const __bf16*)x, (const float*)w, (const float*)mean,
-          (const float*)rstd, (const __bf16*)dy, (__bf16*)dx, (float*)dw,
-          (float*)db, rows, (int)H);
-    OB_LAUNCH_CHECK();
-    return 0;
-  }
+  if (H >= 512 && H <= 1024)
+    return ob_layernorm_bwd_res_bf16(x, w, mean, rstd, dy,
+                                     dx_accum ? dx : nullptr, dx, dw, db,
+                                     nullptr, nullptr, rows, H, stream);
   const int grid = (int)((rows + BLN_CHUNK - 1) / BLN_CHUNK);
   if (dx_accum)
     k_ln_bwd_bf16<true><<<grid, 256, 0, S(stream)>>>(
@@ -959,6 +840,256 @@ extern "C" int ob_layernorm_bwd_bf16(const void* x, const void* w,
         (const float*)rstd, (const __bf16*)dy, (__bf16*)dx, (float*)dw,
         (float*)db, rows, (int)H);
   OB_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Fused ln backward: dx = bf16(res + v) with a separate read-only residual
+// source, plus two optional bias-grad side sums taken from registers:
+// sres += colsum(res), sdx += colsum(dx as rounded to bf16).  res may alias
+// dx (every element is read and written by the same lane), so neither is
+// restrict-qualified.
+//
+// Wave-per-row (H in [512, 1024]): a wave owns its rows outright, the row
+// reductions are wave shfl ladders over ROW PAIRS (two rows' ladders
+// interleave), 16-B vector loads throughout.  8 waves per block, two row
+// pairs per wave (32 rows per block, two waves per SIMD): the kernel is
+// bound by the load -> ladder -> store latency chain, not by bytes, so it
+// wants more rows in flight per CU than the 4-wave, four-pairs-in-sequence
+// kernel it replaces (figures in DESIGN.md).  The column accumulators (dw,
+// db, sres, sdx) fold lane registers -> one LDS row per wave -> one global
+// atomic per column per block.
+// ---------------------------------------------------------------------------
+#define BLNR_WAVES 8
+#define BLNR_WROWS 4
+#define BLNR_ROWS (BLNR_WAVES * BLNR_WROWS)
+#define BLNR_MAXGRID 1024
+
+template <bool HAS_RES, bool SUMS>
+__global__ __launch_bounds__(64 * BLNR_WAVES) void k_ln_bwd_bf16_rs(
+    const __bf16* __restrict__ x, const float* __restrict__ w,
+    const float* __restrict__ mean, const float* __restrict__ rstd,
+    const __bf16* __restrict__ dy, const __bf16* res, __bf16* dx,
+    float* o0, float* o1, float* o2, float* o3, int64_t rows, int H) {
+  constexpr int NV = SUMS ? 4 : 2;
+  constexpr int UNR = (SUMS && HAS_RES) ? 1 : 2;
+  __shared__ float red[BLNR_WAVES][1024];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int c0 = lane * 8, c1 = (lane + 64) * 8;
+  const bool has1 = c1 < H;
+  float acc[4][2][8] = {};  // dw, db, sres, sdx
+  float(&accw)[2][8] = acc[0];
+  float(&accb)[2][8] = acc[1];
+  float(&accr)[2][8] = acc[2];
+  float(&accx)[2][8] = acc[3];
+  float wv0[8], wv1[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    wv0[j] = w[c0 + j];
+    wv1[j] = has1 ? w[c1 + j] : 0.f;
+  }
+  const int64_t nchunks = (rows + BLNR_ROWS - 1) / BLNR_ROWS;
+  for (int64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+    const int64_t r0 = chunk * BLNR_ROWS + wid;
+    // the two pairs unroll (loads of the second hoist over the first's
+    // math) except with all four accumulator sets live, which would spill
+#pragma unroll UNR
+    for (int i = 0; i < BLNR_WROWS; i += 2) {
+      const int64_t rowa = r0 + (int64_t)i * BLNR_WAVES;
+      const int64_t rowb = r0 + (int64_t)(i + 1) * BLNR_WAVES;
+      if (rowa >= rows) break;
+      const bool hb = rowb < rows;
+      const int64_t oa = rowa * H, ob = (hb ? rowb : rowa) * H;
+      const float mua = mean[rowa], rsa = rstd[rowa];
+      const float mub = hb ? mean[rowb] : 0.f, rsb = hb ? rstd[rowb] : 0.f;
+      const uint4 xa0 = *reinterpret_cast<const uint4*>(x + oa + c0);
+      const uint4 ya0 = *reinterpret_cast<const uint4*>(dy + oa + c0);
+      const uint4 xb0 = *reinterpret_cast<const uint4*>(x + ob + c0);
+      const uint4 yb0 = *reinterpret_cast<const uint4*>(dy + ob + c0);
+      uint4 xa1 = {}, ya1 = {}, xb1 = {}, yb1 = {};
+      uint4 ra0 = {}, rb0 = {}, ra1 = {}, rb1 = {};
+      if (HAS_RES) {
+        ra0 = *reinterpret_cast<const uint4*>(res + oa + c0);
+        rb0 = *reinterpret_cast<const uint4*>(res + ob + c0);
+      }
+      if (has1) {
+        xa1 = *reinterpret_cast<const uint4*>(x + oa + c1);
+        ya1 = *reinterpret_cast<const uint4*>(dy + oa + c1);
+        xb1 = *reinterpret_cast<const uint4*>(x + ob + c1);
+        yb1 = *reinterpret_cast<const uint4*>(dy + ob + c1);
+        if (HAS_RES) {
+          ra1 = *reinterpret_cast<const uint4*>(res + oa + c1);
+          rb1 = *reinterpret_cast<const uint4*>(res + ob + c1);
+        }
+      }
+      float s1a = 0.f, s2a = 0.f, s1b = 0.f, s2b = 0.f;
+      float xha0[8], dya0[8], xha1[8], dya1[8];
+      float xhb0[8], dyb0[8], xhb1[8], dyb1[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        xha0[j] = (bf2f(bf_extract(xa0, j)) - mua) * rsa;
+        dya0[j] = bf2f(bf_extract(ya0, j));
+        xhb0[j] = (bf2f(bf_extract(xb0, j)) - mub) * rsb;
+        dyb0[j] = bf2f(bf_extract(yb0, j));
+        s1a += dya0[j] * wv0[j] * xha0[j];
+        s2a += dya0[j] * wv0[j];
+        s1b += dyb0[j] * wv0[j] * xhb0[j];
+        s2b += dyb0[j] * wv0[j];
+        accw[0][j] += dya0[j] * xha0[j];
+        accb[0][j] += dya0[j];
+        if (hb) {
+          accw[0][j] += dyb0[j] * xhb0[j];
+          accb[0][j] += dyb0[j];
+        }
+      }
+      if (has1) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          xha1[j] = (bf2f(bf_extract(xa1, j)) - mua) * rsa;
+          dya1[j] = bf2f(bf_extract(ya1, j));
+          xhb1[j] = (bf2f(bf_extract(xb1, j)) - mub) * rsb;
+          dyb1[j] = bf2f(bf_extract(yb1, j));
+          s1a += dya1[j] * wv1[j] * xha1[j];
+          s2a += dya1[j] * wv1[j];
+          s1b += dyb1[j] * wv1[j] * xhb1[j];
+          s2b += dyb1[j] * wv1[j];
+          accw[1][j] += dya1[j] * xha1[j];
+          accb[1][j] += dya1[j];
+          if (hb) {
+            accw[1][j] += dyb1[j] * xhb1[j];
+            accb[1][j] += dyb1[j];
+          }
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        s1a += __shfl_xor(s1a, o, 64);
+        s2a += __shfl_xor(s2a, o, 64);
+        s1b += __shfl_xor(s1b, o, 64);
+        s2b += __shfl_xor(s2b, o, 64);
+      }
+      const float m1a = s1a / H, m2a = s2a / H;
+      const float m1b = s1b / H, m2b = s2b / H;
+      float oxa[16], oxb[16];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float ra = HAS_RES ? bf2f(bf_extract(ra0, j)) : 0.f;
+        const float rb = HAS_RES ? bf2f(bf_extract(rb0, j)) : 0.f;
+        // round to bf16 here: sdx sums exactly what is stored
+        oxa[j] = bf2f((__bf16)(
+            ra + rsa * (dya0[j] * wv0[j] - m2a - xha0[j] * m1a)));
+        oxb[j] = bf2f((__bf16)(
+            rb + rsb * (dyb0[j] * wv0[j] - m2b - xhb0[j] * m1b)));
+        if (SUMS) {
+          accr[0][j] += ra;
+          accx[0][j] += oxa[j];
+          if (hb) {
+            accr[0][j] += rb;
+            accx[0][j] += oxb[j];
+          }
+        }
+      }
+      if (has1) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float ra = HAS_RES ? bf2f(bf_extract(ra1, j)) : 0.f;
+          const float rb = HAS_RES ? bf2f(bf_extract(rb1, j)) : 0.f;
+          oxa[8 + j] = bf2f((__bf16)(
+              ra + rsa * (dya1[j] * wv1[j] - m2a - xha1[j] * m1a)));
+          oxb[8 + j] = bf2f((__bf16)(
+              rb + rsb * (dyb1[j] * wv1[j] - m2b - xhb1[j] * m1b)));
+          if (SUMS) {
+            accr[1][j] += ra;
+            accx[1][j] += oxa[8 + j];
+            if (hb) {
+              accr[1][j] += rb;
+              accx[1][j] += oxb[8 + j];
+            }
+          }
+        }
+      }
+      *reinterpret_cast<uint4*>(dx + oa + c0) = bf_pack8(&oxa[0]);
+      if (has1) *reinterpret_cast<uint4*>(dx + oa + c1) = bf_pack8(&oxa[8]);
+      if (hb) {
+        *reinterpret_cast<uint4*>(dx + ob + c0) = bf_pack8(&oxb[0]);
+        if (has1) *reinterpret_cast<uint4*>(dx + ob + c1) = bf_pack8(&oxb[8]);
+      }
+    }
+  }
+  // per vector: every wave parks its lane accumulators in its own LDS row
+  // (16-B stores), then the block folds the 8 rows column-wise and adds
+  // one value per column to the fp32 vector (null: not asked for)
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const float(&a0)[8] = acc[v][0];
+    const float(&a1)[8] = acc[v][1];
+    float* const out = v == 0 ? o0 : v == 1 ? o1 : v == 2 ? o2 : o3;
+    *reinterpret_cast<float4*>(&red[wid][c0]) =
+        make_float4(a0[0], a0[1], a0[2], a0[3]);
+    *reinterpret_cast<float4*>(&red[wid][c0 + 4]) =
+        make_float4(a0[4], a0[5], a0[6], a0[7]);
+    if (has1) {
+      *reinterpret_cast<float4*>(&red[wid][c1]) =
+          make_float4(a1[0], a1[1], a1[2], a1[3]);
+      *reinterpret_cast<float4*>(&red[wid][c1 + 4]) =
+          make_float4(a1[4], a1[5], a1[6], a1[7]);
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < H; c += 64 * BLNR_WAVES) {
+      float t = 0.f;
+#pragma unroll
+      for (int k = 0; k < BLNR_WAVES; ++k) t += red[k][c];
+      if (out) atomicAdd(&out[c], t);
+    }
+    __syncthreads();
+  }
+}
+
+// dx = bf16(res + ln_bwd(x, dy)) (res null: no residual; res may equal dx);
+// dw/db += as ob_layernorm_bwd_bf16; sum_res += colsum(res) and sum_dx +=
+// colsum(dx) when non-null.  Widths outside the wave path compose the
+// unfused kernels and give the same results.
+extern "C" int ob_layernorm_bwd_res_bf16(const void* x, const void* w,
+                                         const void* mean, const void* rstd,
+                                         const void* dy, const void* res,
+                                         void* dx, void* dw, void* db,
+                                         void* sum_res, void* sum_dx,
+                                         int64_t rows, int64_t H,
+                                         void* stream) {
+  if (H > 2048) return ob_fail("ln_bwd_bf16: H > 2048 unsupported");
+  if (H % 8) return ob_fail("ln_bwd_bf16: H must be a multiple of 8");
+  if (sum_res && !res) return ob_fail("ln_bwd_res_bf16: sum_res needs res");
+  if (rows <= 0) return 0;
+  if (H >= 512 && H <= 1024) {
+    const bool sums = sum_res || sum_dx;
+    const int64_t nchunks = (rows + BLNR_ROWS - 1) / BLNR_ROWS;
+    const int grid = (int)bmin64(nchunks, BLNR_MAXGRID);
+#define OB_LNRS(R_, S_)                                                     \
+  k_ln_bwd_bf16_rs<R_, S_><<<grid, 64 * BLNR_WAVES, 0, S(stream)>>>(        \
+      (const __bf16*)x, (const float*)w, (const float*)mean,                \
+      (const float*)rstd, (const __bf16*)dy, (const __bf16*)res,            \
+      (__bf16*)dx, (float*)dw, (float*)db, (float*)sum_res, (float*)sum_dx, \
+      rows, (int)H)
+    if (res) {
+      if (sums) OB_LNRS(true, true);
+      else OB_LNRS(true, false);
+    } else {
+      if (sums) OB_LNRS(false, true);
+      else OB_LNRS(false, false);
+    }
+#undef OB_LNRS
+    OB_LAUNCH_CHECK();
+    return 0;
+  }
+  // composed path: colsum(res) first (res may alias dx), copy, ln, colsum
+  if (sum_res && ob_colsum_bf16(res, sum_res, rows, H, stream)) return 1;
+  if (res && res != dx)
+    OB_HIP(hipMemcpyAsync(dx, res, (size_t)(rows * H) * sizeof(__bf16),
+                          hipMemcpyDeviceToDevice, S(stream)));
+  if (ob_layernorm_bwd_bf16(x, w, mean, rstd, dy, dx, dw, db, rows, H,
+                            res ? 1 : 0, stream))
+    return 1;
+  if (sum_dx && ob_colsum_bf16(dx, sum_dx, rows, H, stream)) return 1;
   return 0;
 }
 
@@ -1267,6 +1398,103 @@ extern "C" int ob_colsum_bf16(const void* X, void* db, int64_t M, int64_t N,
   }
   OB_LAUNCH_CHECK();
   return 0;
+}
+
+// gelu backward fused with the bias grad of the GEMM that produced u:
+// du = dg * gelu'(u) and db[c] += sum_r du[r][c], summed over the
+// bf16-rounded du (what ob_colsum_bf16(du) summed).  Block = 16 col-threads
+// x 16 row-threads over a 128-col x 128-row tile; a thread owns 8 fixed
+// columns and keeps 4 rows (8 independent 16-B loads) in flight.  Column
+// partials go registers -> wave shfl -> LDS -> one atomic per column per
+// block.  du may alias dg (same lane reads and writes an element).
+#define BGC_ROWS 128
+// gelu'(x) with tanh(z) = 1 - 2 / (1 + exp(2z)) on the hardware exp2 / rcp
+// (about 15 VALU ops against about 45 for the branchy library tanhf: at
+// [8192, 3072] the library form makes the kernel VALU-bound).
+// t enters d only added to O(1) terms, so the ~1e-7 absolute error of the
+// fast form is far below the bf16 rounding of du; exp2 overflow gives
+// rcp(inf) = 0, t = 1, and 1 - t*t = 0 (no inf * 0).
+__device__ __forceinline__ float bgelu_grad_fast(float x) {
+  constexpr float L2E2 = 2.8853900817779268f;  // 2 * log2(e)
+  const float x2 = x * x;
+  const float e = __builtin_amdgcn_exp2f(
+      x * (BGELU_K * L2E2 + BGELU_K * BGELU_C * L2E2 * x2));
+  const float t = 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + e);
+  return 0.5f * (1.f + t) + 0.5f * x * (1.f - t * t) *
+                                (BGELU_K + 3.f * BGELU_K * BGELU_C * x2);
+}
+__global__ __launch_bounds__(256) void k_gelu_bwd_cs_bf16(
+    const __bf16* __restrict__ u, const __bf16* dg, __bf16* du,
+    float* __restrict__ db, int64_t M, int64_t N) {
+  __shared__ float red[4][128];
+  const int tid = threadIdx.x;
+  const int cg = tid & 15, rt = tid >> 4;  // col-thread, row-thread
+  const int lane = tid & 63, wv = tid >> 6;
+  const int64_t c0 = (int64_t)blockIdx.x * 128 + cg * 8;
+  const int64_t rbase = (int64_t)blockIdx.y * BGC_ROWS + rt;
+  float acc[8] = {0};
+  if (c0 < N) {  // N % 8 == 0: the whole 8-column group is in range
+    for (int it = 0; it < BGC_ROWS / 64; ++it) {
+      uint4 uin[4] = {}, gin[4] = {};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int64_t r = rbase + it * 64 + i * 16;
+        if (r < M) {
+          uin[i] = *reinterpret_cast<const uint4*>(u + r * N + c0);
+          gin[i] = *reinterpret_cast<const uint4*>(dg + r * N + c0);
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int64_t r = rbase + it * 64 + i * 16;
+        if (r < M) {
+          float out[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const float x = bf2f(bf_extract(uin[i], j));
+            const float d = bgelu_grad_fast(x);
+            out[j] = bf2f((__bf16)(bf2f(bf_extract(gin[i], j)) * d));
+            acc[j] += out[j];
+          }
+          *reinterpret_cast<uint4*>(du + r * N + c0) = bf_pack8_(out);
+        }
+      }
+    }
+  }
+  // wave: fold the 4 row-slots (lanes cg + 16*s, s = 0..3)
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    acc[j] += __shfl_down(acc[j], 32, 64);
+    acc[j] += __shfl_down(acc[j], 16, 64);
+  }
+  if (lane < 16) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) red[wv][lane * 8 + j] = acc[j];
+  }
+  __syncthreads();
+  if (tid < 128) {
+    const int64_t c = (int64_t)blockIdx.x * 128 + tid;
+    if (c < N)
+      atomicAdd(&db[c],
+                red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]);
+  }
+}
+
+extern "C" int ob_gelu_bwd_colsum_bf16(const void* u, const void* dg,
+                                       void* du, void* db, int64_t M,
+                                       int64_t N, void* stream) {
+  if (M <= 0 || N <= 0) return 0;
+  if (N % 8 == 0) {
+    dim3 grid((unsigned)((N + 127) / 128),
+              (unsigned)((M + BGC_ROWS - 1) / BGC_ROWS));
+    k_gelu_bwd_cs_bf16<<<grid, 256, 0, S(stream)>>>(
+        (const __bf16*)u, (const __bf16*)dg, (__bf16*)du, (float*)db, M, N);
+    OB_LAUNCH_CHECK();
+    return 0;
+  }
+  // other widths compose the unfused kernels
+  if (ob_gelu_bwd_bf16(u, dg, du, M * N, stream)) return 1;
+  return ob_colsum_bf16(du, db, M, N, stream);
 }
 
 __global__ __launch_bounds__(256) void k_embed_fwd_bf16(

@@ -636,14 +636,13 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   const __bf16* sh = l->shadows;
   const BlockParams bp = block_params(H);
 
+  // ln1 reads the input once and also writes its stash copy x
   __bf16* x = (__bf16*)(st + l->o_x);
-  OB_HIP(hipMemcpyAsync(x, in, BS * H * sizeof(__bf16),
-                        hipMemcpyDeviceToDevice, S(stream)));
   __bf16* ln1 = (__bf16*)(st + l->o_ln1);
   if (OB_PROF(OB_PF_LN, stream,
-              ob_layernorm_fwd_bf16(x, p + bp.ln1_w, p + bp.ln1_b, ln1,
-                                    st + l->o_mean1, st + l->o_rstd1, BS, H,
-                                    1e-5f, stream)))
+              ob_layernorm_fwd_copy_bf16(in, p + bp.ln1_w, p + bp.ln1_b, ln1,
+                                         x, st + l->o_mean1, st + l->o_rstd1,
+                                         BS, H, 1e-5f, stream)))
     return 1;
   __bf16* qkv = (__bf16*)(st + l->o_qkv);
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
@@ -723,15 +722,14 @@ static int final_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   if (!labels) return ob_fail("final_forward_bf16: labels required");
 
   __bf16* x = (__bf16*)(st + l->o_x);
-  OB_HIP(hipMemcpyAsync(x, in, BS * H * sizeof(__bf16),
-                        hipMemcpyDeviceToDevice, S(stream)));
   int64_t* labs = l->ids + (int64_t)slot * (int64_t)l->d.max_batch * Sq;
   OB_HIP(hipMemcpyAsync(labs, labels, BS * sizeof(int64_t),
                         hipMemcpyDeviceToDevice, S(stream)));
   __bf16* lnf = (__bf16*)(st + l->o_ln1);
   if (OB_PROF(OB_PF_LN, stream,
-              ob_layernorm_fwd_bf16(x, p + 0, p + H, lnf, st + l->o_mean1,
-                                    st + l->o_rstd1, BS, H, 1e-5f, stream)))
+              ob_layernorm_fwd_copy_bf16(in, p + 0, p + H, lnf, x,
+                                         st + l->o_mean1, st + l->o_rstd1,
+                                         BS, H, 1e-5f, stream)))
     return 1;
   __bf16* logits = (__bf16*)(st + l->o_logits);
   // N = v_pad (zero-padded shadow rows -> padded logits are exactly 0)
@@ -776,16 +774,16 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   __bf16* DQKV = (__bf16*)g_ws.dqkv;
   __bf16* DP = (__bf16*)g_ws.dp;
 
-  // The dW family (transposes + atomic GEMMs + bias colsums) has no
-  // consumer inside this call and no effect on the dX chain: it runs on
+  // The dW family (transposes + atomic GEMMs + the qkv bias colsum) has
+  // no consumer inside this call and no effect on the dX chain (the other
+  // three bias grads are side sums of the main-stream gelu / ln2 backward
+  // kernels): it runs on
   // g_side, overlapped under the dX/attention work, fenced by events at
   // the producer edges and JOINED at the end of the call (the g_ws
   // buffers it reads are reused by the next microbatch's backward).
   void* const side = (void*)g_side.stream;
   OB_SIDE_FENCE(S(stream), g_side.stream);  // entry state (dout ready)
 
-  OB_HIP(hipMemcpyAsync(din, dout, BS * H * sizeof(__bf16),
-                        hipMemcpyDeviceToDevice, S(stream)));
   // ---- MLP ----
   if (OB_PROF(OB_PF_GEMM_DX, stream,
               gemm_bf(0, 1, BS, 4 * H, H, 1.f, dout, H, 0, 0, sh + l->sh_mp,
@@ -796,29 +794,30 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
               dw_bf16_ws(gact, 4 * H, dout, H, BS, g + bp.w_mlpproj, H,
                          g_ws.s1, g_ws.s2, side)))
     return 1;
-  if (OB_PROF(OB_PF_ELEM, side,
-              ob_colsum_bf16(dout, g + bp.b_mlpproj, BS, H, side)))
-    return 1;
+  // gelu backward also sums its output columns into the b_fc grad
   if (OB_PROF(OB_PF_ELEM, stream,
-              ob_gelu_bwd_bf16(u, DY4, DY4, BS * 4 * H, stream)))
+              ob_gelu_bwd_colsum_bf16(u, DY4, DY4, g + bp.b_fc, BS, 4 * H,
+                                      stream)))
     return 1;
   OB_SIDE_FENCE(S(stream), g_side.stream);  // DY4 post-gelu
   if (OB_PROF(OB_PF_GEMM_DW, side,
               dw_bf16_ws(ln2, H, DY4, 4 * H, BS, g + bp.w_fc, 4 * H, g_ws.s1,
                          g_ws.s2, side)))
     return 1;
-  if (OB_PROF(OB_PF_ELEM, side,
-              ob_colsum_bf16(DY4, g + bp.b_fc, BS, 4 * H, side)))
-    return 1;
   if (OB_PROF(OB_PF_GEMM_DX, stream,
               gemm_bf(0, 1, BS, H, 4 * H, 1.f, DY4, 4 * H, 0, 0,
                       sh + l->sh_fc, 4 * H, 0, 0, DLN, H, 0, 0, 1, 1,
                       nullptr, nullptr, 0, 1, stream)))
     return 1;
+  // ln2 backward takes the residual straight from dout (din = dout + v,
+  // no entry copy) and sums both streams it holds in registers: dout
+  // columns -> b_mlpproj grad, din columns -> b_attnproj grad
   if (OB_PROF(OB_PF_LN, stream,
-              ob_layernorm_bwd_bf16(hmid, p + bp.ln2_w, st + l->o_mean2,
-                                    st + l->o_rstd2, DLN, din, g + bp.ln2_w,
-                                    g + bp.ln2_b, BS, H, 1, stream)))
+              ob_layernorm_bwd_res_bf16(hmid, p + bp.ln2_w, st + l->o_mean2,
+                                        st + l->o_rstd2, DLN, dout, din,
+                                        g + bp.ln2_w, g + bp.ln2_b,
+                                        g + bp.b_mlpproj, g + bp.b_attnproj,
+                                        BS, H, stream)))
     return 1;
   // ---- attention projection ----
   OB_SIDE_FENCE(S(stream), g_side.stream);  // din post-ln2-bwd
@@ -830,9 +829,6 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   if (OB_PROF(OB_PF_GEMM_DW, side,
               dw_bf16_ws(am, H, din, H, BS, g + bp.w_attnproj, H, g_ws.s1,
                          g_ws.s2, side)))
-    return 1;
-  if (OB_PROF(OB_PF_ELEM, side,
-              ob_colsum_bf16(din, g + bp.b_attnproj, BS, H, side)))
     return 1;
   // din is re-updated by the final ln1 backward: the main stream must
   // not reach it before the side finished reading din
