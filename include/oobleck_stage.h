@@ -118,6 +118,59 @@ int ob_adamw_step(void* p, const void* g, void* m, void* v, int64_t n,
                   int32_t step, float lr, float beta1, float beta2, float eps,
                   float weight_decay, void* stream);
 
+/* ---- global gradient-norm clipping (the `# amp enable check: gradient
+ * clipping` seam the reference left open at pipeline.py:241-244) ----------
+ *
+ * Three calls per optimizer step, all asynchronous on `stream`, no host
+ * synchronisation: per-tensor square norms -> (the host all-reduces the
+ * per-layer vector over the pipeline's ranks) -> ob_clip_finish -> one
+ * ob_adamw_step_scaled per flat buffer.  The caller owns every buffer.
+ *
+ * Semantics: the norm is taken over the gradient the optimizer consumes
+ * (after the data-parallel all-reduce that is the SUM over replicas; the
+ * reference never averages).  It is bit-identical across replicas whose
+ * layers have the same shard count, whatever their stage splits.  Where
+ * shard counts differ, a layer's fp64 partial sums associate differently:
+ * totals agree to fp64 rounding, which can in principle move the fp32
+ * coefficient by one ulp. */
+
+/* Workspace size of ob_sqnorm_multi_f32, in doubles, for `n` tensors of
+ * counts[i] elements. */
+int64_t ob_sqnorm_ws_count(const int64_t* counts, int32_t n);
+
+/* out[out_index[i]] = sum_j g_i[j]^2 in fp64 for n fp32 device buffers.
+ * ptrs / counts / out_index are HOST arrays (out_index NULL = identity);
+ * ws (ob_sqnorm_ws_count doubles) and out are device fp64.  Output slots not
+ * named in out_index are left untouched; a 0-element tensor writes 0.
+ * Products and sums are fp64 from the first multiply.  Deterministic: the
+ * result for a tensor depends only on its values and element count, never on
+ * the run, the pointer's alignment (4-byte alignment is required, 16-byte
+ * enables vector loads) or the other tensors in the call.  No atomics. */
+int ob_sqnorm_multi_f32(const void* const* ptrs, const int64_t* counts,
+                        const int32_t* out_index, int32_t n, void* ws,
+                        void* out, void* stream);
+
+/* Adds sq[0..n) (device fp64) in index order and writes the 4-double device
+ * record stats = {total_sq, norm, coef, skipped_steps}:
+ *   coef = (float)min(1, max_norm / (norm + 1e-6))   -- the semantics of
+ *   torch.nn.utils.clip_grad_norm_, exactly 1.0f when norm + 1e-6 <= max_norm.
+ * If the total is not finite, coef is the SKIP MARKER -1.0 (any coef < 0)
+ * and skipped_steps is incremented; otherwise skipped_steps is left as is
+ * (the caller zero-initialises the record once).  max_norm must be > 0. */
+int ob_clip_finish(const void* sq, int32_t n, float max_norm, void* stats,
+                   void* stream);
+
+/* ob_adamw_step over g[i] * coef, with coef read on the device from the
+ * record ob_clip_finish wrote; otherwise the same arithmetic (coef == 1.0f
+ * is bit-identical to ob_adamw_step).  Deviation from torch's in-place
+ * clip: the scaled gradient is NOT written back to g (it would add 4 B/param
+ * of traffic and the caller zeroes g right after the step).  On the skip
+ * marker none of p, m, v is touched. */
+int ob_adamw_step_scaled(void* p, const void* g, void* m, void* v, int64_t n,
+                         int32_t step, float lr, float beta1, float beta2,
+                         float eps, float weight_decay, const void* clip_stats,
+                         void* stream);
+
 /* ---- standalone kernel entry points (parity tests + roofline probes) ---- */
 
 /* C[M,N] (+)= alpha * op(A)[M,K] @ op(B)[K,N] + bias[n] + R[m,n]
@@ -186,7 +239,7 @@ int ob_bf16_to_f32(const void* x, void* y, int64_t n, void* stream);
 
 /* ---- in-step profiling (measurement only; off by default) ---------------
  * When enabled, each wrapped launch region inside ob_layer_forward/backward
- * and ob_adamw_step is bracketed by HIP events on its launch stream and
+ * and ob_adamw_step (and the clipping calls, family 10) is bracketed by HIP events on its launch stream and
  * accumulated per family, so the bench can report the production dispatch's
  * in-step per-launch time (roofline) and a per-family step-time split.
  * Families (ob_profile_read's `fam`): 0 fc_fwd_gemm (the roofline kernel),

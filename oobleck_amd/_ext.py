@@ -43,6 +43,14 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.ob_layer_refresh_weights.argtypes = [vp, vp]
     lib.ob_adamw_step.argtypes = [vp, vp, vp, vp, i64, i32, f32, f32, f32,
                                   f32, f32, vp]
+    lib.ob_sqnorm_ws_count.restype = i64
+    lib.ob_sqnorm_ws_count.argtypes = [ctypes.POINTER(i64), i32]
+    lib.ob_sqnorm_multi_f32.argtypes = [ctypes.POINTER(vp),
+                                        ctypes.POINTER(i64),
+                                        ctypes.POINTER(i32), i32, vp, vp, vp]
+    lib.ob_clip_finish.argtypes = [vp, i32, f32, vp, vp]
+    lib.ob_adamw_step_scaled.argtypes = [vp, vp, vp, vp, i64, i32, f32, f32,
+                                         f32, f32, f32, vp, vp]
     lib.ob_gemm_f32.argtypes = [i32, i32, i64, i64, i64, f32, vp, i64, i64,
                                 i64, vp, i64, i64, i64, f32, vp, i64, i64,
                                 i64, i64, i64, vp, vp, i32, i32, vp]

@@ -49,6 +49,9 @@ class TrainingConfig:
     adam_eps: float = 1e-8
     weight_decay: float = 0.0
     warmup_steps: int = 0
+    # global gradient-norm clipping (HF TrainingArguments.max_grad_norm; the
+    # reference leaves the seam open at pipeline.py:241-244).  0 = off.
+    max_grad_norm: float = 0.0
 
     @property
     def num_microbatches(self) -> int:

@@ -68,6 +68,21 @@ void ob_prof_end(int fam, int slot, hipStream_t s);
     _r;                                                                 \
   })
 
+// One element of the fused AdamW update, shared by k_adamw (ob_kernels.hip)
+// and k_adamw_scaled (ob_optim.hip) so the two cannot drift apart: gi is the
+// gradient the update consumes (raw, or raw * clip coefficient).
+__device__ __forceinline__ void ob_adamw_update(
+    float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+    int64_t i, float gi, float wd_factor, float step_size, float inv_sqrt_bc2,
+    float beta1, float beta2, float eps) {
+  float mi = beta1 * m[i] + (1.f - beta1) * gi;
+  float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
+  m[i] = mi;
+  v[i] = vi;
+  const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
+  p[i] = p[i] * wd_factor - step_size * mi / denom;
+}
+
 // internal launchers used by the layer orchestration (same semantics as the
 // public ob_* wrappers but C++ linkage, no error wrapping duplication).
 int ob_embed_fwd_f32(const int64_t* ids, const float* wte, const float* wpe,

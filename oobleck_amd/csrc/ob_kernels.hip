@@ -1046,13 +1046,8 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p,
                                                float beta2, float eps) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * 256) {
-    const float gi = g[i];
-    float mi = beta1 * m[i] + (1.f - beta1) * gi;
-    float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-    p[i] = p[i] * wd_factor - step_size * mi / denom;
+    ob_adamw_update(p, m, v, i, g[i], wd_factor, step_size, inv_sqrt_bc2,
+                    beta1, beta2, eps);
   }
 }
 

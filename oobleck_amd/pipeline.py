@@ -66,6 +66,21 @@ class PipelineExecution:
         self.total_loss: torch.Tensor | None = None
         self._optimizer = optimizer
         self._lr_scheduler = lr_scheduler
+        # a clipping optimizer needs the norm over the WHOLE pipeline, not
+        # this stage: hand it the pipeline-wide group, or refuse loudly
+        # (test doubles without max_grad_norm pass through untouched)
+        if getattr(optimizer, "max_grad_norm", 0) > 0 and \
+                len(pipeline._ranks) > 1 and \
+                getattr(optimizer, "clip_group", None) is None:
+            group = getattr(pipeline, "_clip_pg", None)
+            if group is None:
+                raise RuntimeError(
+                    "optimizer clips by the global gradient norm but this "
+                    f"{len(pipeline._ranks)}-rank pipeline has no process "
+                    "group for it: set TrainingConfig.max_grad_norm > 0 "
+                    "before initialize_distributed_pipeline() (clipping by "
+                    "the stage-local norm would be silently wrong)")
+            optimizer.set_clip_group(group)
         import torch as _torch
         self._act_dtype = getattr(layers[0], "act_dtype", _torch.float32) \
             if layers else _torch.float32
@@ -411,6 +426,12 @@ class OobleckPipeline:
                     pipeline=self, process_group=pg,
                     prev_rank=unique[idx - 1] if idx > 0 else None,
                     next_rank=unique[idx + 1] if idx < len(unique) - 1 else None)
+        # one group over ALL of this pipeline's ranks for the global
+        # gradient norm — only when clipping is on (the value is the same on
+        # every rank, so the collective new_group order stays consistent)
+        self._clip_pg = None
+        if self.training_cfg.max_grad_norm > 0:
+            self._clip_pg = dist.new_group(self._ranks)
 
     def initialize_execution(self, layer_factory, optimizer_factory) -> None:
         """Build this rank's layers and the schedule.
