@@ -77,6 +77,43 @@ int64_t ob_layer_param_count(const ob_layer_desc* desc);
  * HIP device.  Parameters/grads are NOT allocated here — see ob_layer_bind. */
 int ob_layer_create(const ob_layer_desc* desc, ob_layer_t* out);
 
+/* ---- dropout (GPT-2's embd / resid / attn pdrop) --------------------------
+ * Masks are stateless: a keep bit is Philox4x32-10 of (seed, layer_id, site,
+ * tick, element index) -- see DESIGN.md "Dropout masks" for the frozen
+ * definition.  The backward of a slot regenerates the masks of that slot's
+ * forward from the tick the forward used; nothing is stashed.
+ * Sites: 0 embedding output [B,S,H], 1 attention probabilities [B,nh,S,S],
+ * 2 attention-projection output [B,S,H], 3 MLP-projection output [B,S,H]. */
+enum {
+  OB_DROP_EMBD = 0,
+  OB_DROP_ATTN = 1,
+  OB_DROP_RESID_ATTN = 2,
+  OB_DROP_RESID_MLP = 3
+};
+
+typedef struct {
+  float embd_pdrop;     /* EMBED layers; each probability in [0,1) */
+  float resid_pdrop;    /* BLOCK layers, sites 2 and 3 */
+  float attn_pdrop;     /* BLOCK layers, site 1; > 0 takes the materialized-P
+                           attention path (no flash) */
+  int32_t layer_id;     /* 0 <= layer_id < 2^24 */
+  uint64_t seed;
+} ob_dropout_desc;
+
+/* ob_layer_create with dropout.  drop NULL or all probabilities 0 is exactly
+ * ob_layer_create: the same kernels are launched and nothing else. */
+int ob_layer_create_ex(const ob_layer_desc* desc, const ob_dropout_desc* drop,
+                       ob_layer_t* out);
+
+/* Training mode (default 1).  0 makes dropout inert (eval): forwards run
+ * today's dropout-free path and do not advance the tick. */
+int ob_layer_set_training(ob_layer_t l, int on);
+
+/* Tick of the NEXT forward (default 0); each training forward of a layer
+ * with dropout then post-increments it.  The tick a forward used is kept per
+ * slot, and the backward of slot s uses slot s's tick. */
+int ob_layer_set_dropout_tick(ob_layer_t l, uint64_t tick);
+
 /* Bind caller-owned device fp32 buffers of ob_layer_param_count() elements:
  * params (read/write: forward reads, adam writes) and grads (backward
  * ACCUMULATES, caller zeroes between steps).  Mirrors flat_param /
@@ -215,6 +252,37 @@ int ob_gelu_bwd_f32(const void* u, const void* dg, void* du, int64_t n,
 /* db[n] += sum_m X[m,n] (bias gradient). */
 int ob_colsum_f32(const void* X, void* db, int64_t M, int64_t N, void* stream);
 
+/* Dropout kernels over the mask of (seed, layer_id, site, tick), element
+ * index = flat index into the tensor; p in [0,1); n (or M*N) <= 2^34.
+ * keep_u8[e] = 1 if element e is kept. */
+int ob_dropout_mask(uint64_t seed, int32_t layer_id, int32_t site,
+                    uint64_t tick, float p, int64_t n, void* keep_u8,
+                    void* stream);
+/* y = keep * x / (1-p); y may alias x. */
+int ob_dropout_scale_f32(uint64_t seed, int32_t layer_id, int32_t site,
+                         uint64_t tick, float p, const void* x, void* y,
+                         int64_t n, void* stream);
+int ob_dropout_scale_bf16(uint64_t seed, int32_t layer_id, int32_t site,
+                          uint64_t tick, float p, const void* x, void* y,
+                          int64_t n, void* stream);
+/* y = res + keep * t / (1-p); y may alias t. */
+int ob_dropout_add_f32(uint64_t seed, int32_t layer_id, int32_t site,
+                       uint64_t tick, float p, const void* t, const void* res,
+                       void* y, int64_t n, void* stream);
+int ob_dropout_add_bf16(uint64_t seed, int32_t layer_id, int32_t site,
+                        uint64_t tick, float p, const void* t,
+                        const void* res, void* y, int64_t n, void* stream);
+/* dm[M,N] = keep * dy / (1-p) (dm may alias dy); db[n] += sum_m dm[m,n]
+ * (fp32, atomically; on bf16 the bf16-rounded dm is what is summed). */
+int ob_dropout_scale_colsum_f32(uint64_t seed, int32_t layer_id, int32_t site,
+                                uint64_t tick, float p, const void* dy,
+                                void* dm, void* db, int64_t M, int64_t N,
+                                void* stream);
+int ob_dropout_scale_colsum_bf16(uint64_t seed, int32_t layer_id, int32_t site,
+                                 uint64_t tick, float p, const void* dy,
+                                 void* dm, void* db, int64_t M, int64_t N,
+                                 void* stream);
+
 /* ---- bf16 mixed-precision path ------------------------
  * bf16 MFMA GEMM (v_mfma_f32_32x32x16_bf16, fp32 accumulate).  Same
  * call shape as ob_gemm_f32; A/B are bf16; out_kind: 0 = bf16 C,
@@ -245,7 +313,7 @@ int ob_bf16_to_f32(const void* x, void* y, int64_t n, void* stream);
  * Families (ob_profile_read's `fam`): 0 fc_fwd_gemm (the roofline kernel),
  * 1 gemm_fwd_other, 2 gemm_dx, 3 gemm_dw(side stream), 4 flash_fwd,
  * 5 flash_bwd, 6 attn_matmuls(non-flash), 7 layernorm, 8 cross_entropy,
- * 9 elementwise(gelu/colsum/embed), 10 adamw. */
+ * 9 elementwise(gelu/colsum/embed/dropout), 10 adamw. */
 void ob_profile_enable(int on);
 void ob_profile_reset(void);
 int ob_profile_read(int fam, double* total_ms, long long* count);

@@ -27,6 +27,20 @@ class ObLayerDesc(ctypes.Structure):
     ]
 
 
+class ObDropoutDesc(ctypes.Structure):
+    _fields_ = [
+        ("embd_pdrop", ctypes.c_float),
+        ("resid_pdrop", ctypes.c_float),
+        ("attn_pdrop", ctypes.c_float),
+        ("layer_id", ctypes.c_int32),
+        ("seed", ctypes.c_uint64),
+    ]
+
+
+# dropout sites (OB_DROP_* of include/oobleck_stage.h)
+DROP_EMBD, DROP_ATTN, DROP_RESID_ATTN, DROP_RESID_MLP = 0, 1, 2, 3
+
+
 def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
     i64, i32, f32, vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_float, ctypes.c_void_p
     lib.ob_last_error.restype = ctypes.c_char_p
@@ -35,6 +49,22 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.ob_layer_param_count.argtypes = [ctypes.POINTER(ObLayerDesc)]
     lib.ob_layer_create.argtypes = [ctypes.POINTER(ObLayerDesc),
                                     ctypes.POINTER(vp)]
+    u64 = ctypes.c_uint64
+    lib.ob_layer_create_ex.argtypes = [ctypes.POINTER(ObLayerDesc),
+                                       ctypes.POINTER(ObDropoutDesc),
+                                       ctypes.POINTER(vp)]
+    lib.ob_layer_set_training.argtypes = [vp, i32]
+    lib.ob_layer_set_dropout_tick.argtypes = [vp, u64]
+    # (seed, layer_id, site, tick, p) select the mask of every dropout entry
+    key = [u64, i32, i32, u64, f32]
+    lib.ob_dropout_mask.argtypes = key + [i64, vp, vp]
+    lib.ob_dropout_scale_f32.argtypes = key + [vp, vp, i64, vp]
+    lib.ob_dropout_scale_bf16.argtypes = key + [vp, vp, i64, vp]
+    lib.ob_dropout_add_f32.argtypes = key + [vp, vp, vp, i64, vp]
+    lib.ob_dropout_add_bf16.argtypes = key + [vp, vp, vp, i64, vp]
+    lib.ob_dropout_scale_colsum_f32.argtypes = key + [vp, vp, vp, i64, i64, vp]
+    lib.ob_dropout_scale_colsum_bf16.argtypes = key + [vp, vp, vp, i64, i64,
+                                                       vp]
     lib.ob_layer_bind.argtypes = [vp, vp, vp]
     lib.ob_layer_set_batch.argtypes = [vp, i32]
     lib.ob_layer_forward.argtypes = [vp, i32, vp, vp, vp, vp]

@@ -11,9 +11,11 @@ SOURCES = [PKG_DIR / "csrc" / "ob_kernels.hip",
            PKG_DIR / "csrc" / "ob_kernels_bf16.hip",
            PKG_DIR / "csrc" / "ob_blaslt.hip",
            PKG_DIR / "csrc" / "ob_optim.hip",
+           PKG_DIR / "csrc" / "ob_dropout.hip",
            PKG_DIR / "csrc" / "ob_layer.hip"]
 HEADERS = [PKG_DIR.parent / "include" / "oobleck_stage.h",
-           PKG_DIR / "csrc" / "ob_internal.h"]
+           PKG_DIR / "csrc" / "ob_internal.h",
+           PKG_DIR / "csrc" / "ob_philox.h"]
 
 
 def needs_rebuild() -> bool:

@@ -16,6 +16,11 @@ class ModelConfig:
     n_layer: int = 12            # transformer blocks
     n_positions: int = 1024
     vocab_size: int = 50257
+    # GPT-2's dropout probabilities (HF GPT2Config defaults are 0.1 each; the
+    # reference trains with them).  0 = off: the dropout-free kernels run.
+    embd_pdrop: float = 0.0
+    resid_pdrop: float = 0.0
+    attn_pdrop: float = 0.0
 
     @property
     def n_layers_total(self) -> int:
@@ -52,6 +57,9 @@ class TrainingConfig:
     # global gradient-norm clipping (HF TrainingArguments.max_grad_norm; the
     # reference leaves the seam open at pipeline.py:241-244).  0 = off.
     max_grad_norm: float = 0.0
+    # dropout masks are a pure function of (dropout_seed, pipeline id, layer,
+    # site, optimizer step, microbatch, element): no RNG state to carry
+    dropout_seed: int = 0
 
     @property
     def num_microbatches(self) -> int:

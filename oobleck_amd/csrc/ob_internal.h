@@ -95,6 +95,23 @@ int ob_ce_bwd_f32(float* logits_to_dlogits, const int64_t* labels,
                   const float* lse, const float* dloss_or_null, int64_t B,
                   int64_t S, int64_t V, void* stream);
 
+// dropout launchers (ob_dropout.hip), keyed by the site's ob_drop_key
+// (ob_philox.h); bf16 != 0 selects the bf16 kernels.  y may alias x / t.
+struct ob_drop_key;
+int ob_drop_scale(const ob_drop_key& key, int bf16, const void* x, void* y,
+                  int64_t n, void* stream);
+int ob_drop_add(const ob_drop_key& key, int bf16, const void* t,
+                const void* res, void* y, int64_t n, void* stream);
+int ob_drop_scale_colsum(const ob_drop_key& key, int bf16, const void* dy,
+                         void* dm, void* db, int64_t M, int64_t N,
+                         void* stream);
+int ob_embed_fwd_drop(const ob_drop_key& key, int bf16, const int64_t* ids,
+                      const float* wte, const float* wpe, void* out, int64_t B,
+                      int64_t Sq, int64_t H, void* stream);
+int ob_embed_bwd_drop(const ob_drop_key& key, int bf16, const int64_t* ids,
+                      const void* dout, float* dwte, float* dwpe, int64_t B,
+                      int64_t Sq, int64_t H, void* stream);
+
 // bf16-path launchers (defined in ob_kernels_bf16.hip)
 extern "C" {
 int ob_f32_to_bf16_t_ld(const void* x, void* y, int64_t rows, int64_t cols,

@@ -11,9 +11,11 @@
 // The activation stash is slot-indexed so several microbatches can be in
 // flight, matching deepspeed-style pipe buffers (pipeline.py:556-562).
 #include "ob_internal.h"
+#include "ob_philox.h"
 
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int64_t i64min(int64_t a, int64_t b) { return a < b ? a : b; }
@@ -33,8 +35,19 @@ struct Workspace {
   float* t2 = nullptr;
   float* s1 = nullptr;     // side-stream dW transpose buffers (bf16 as
   float* s2 = nullptr;     // floats): the dW family runs on g_side
+  // dropout only (never allocated without it).  pd_f belongs to the
+  // FORWARD (Pd = drop(P) feeding the PV GEMM): under pp1 overlap a forward
+  // runs beside a backward, so it shares nothing with the buffers below.
+  // pd_b is the backward's regenerated Pd; dm1/dm2 hold the masked
+  // projection grads, which the side-stream dW GEMMs read until the
+  // end-of-call join (DATT/DLN are overwritten by the main stream earlier).
+  float* pd_f = nullptr;   // [B*nh, S, S]
+  float* pd_b = nullptr;   // [B*nh, S, S]
+  float* dm1 = nullptr;    // [B, S, H] masked d(hmid), site RESID_ATTN
+  float* dm2 = nullptr;    // [B, S, H] masked dout, site RESID_MLP
   int64_t sz_dp = 0, sz_bsh = 0, sz_bsh2 = 0, sz_dqkv = 0, sz_b4h = 0,
-          sz_t1 = 0, sz_t2 = 0, sz_s1 = 0, sz_s2 = 0;
+          sz_t1 = 0, sz_t2 = 0, sz_s1 = 0, sz_s2 = 0, sz_pd_f = 0,
+          sz_pd_b = 0, sz_dm1 = 0, sz_dm2 = 0;
 };
 static Workspace g_ws;
 
@@ -193,12 +206,34 @@ struct ob_layer {
   // o_p slot holds only the per-row LSE ([Bm*nh, S] floats) instead of
   // the materialized [Bm*nh, S, S] P.
   bool flash = false;
+  // dropout (ob_layer_create_ex); all probabilities 0 = none.  Only the
+  // probabilities that apply to this layer's kind are kept.
+  float p_embd = 0.f, p_resid = 0.f, p_attn = 0.f;
+  int32_t layer_id = 0;
+  uint64_t seed = 0;
+  bool training = true;
+  uint64_t next_tick = 0;
+  // host-side, per slot: whether that slot's forward drew masks, and the
+  // tick it used (calls are enqueued in host order, so the backward of slot
+  // s reads what the forward of slot s wrote)
+  std::vector<uint8_t> slot_drop;
+  std::vector<uint64_t> slot_tick;
 };
+
+static bool has_dropout(const ob_layer* l) {
+  return l->p_embd > 0.f || l->p_resid > 0.f || l->p_attn > 0.f;
+}
+static ob_drop_key drop_key(const ob_layer* l, int slot, int site, float p) {
+  return ob_drop_make_key(l->seed, l->layer_id, site, l->slot_tick[slot], p);
+}
 
 // flash applies when head_dim == 64 and S % 128 == 0 (GPT-2 small and
 // XL both qualify); OB_BF16_FLASH=0 falls back to the materialized-P
 // path.  Decided at create time: it sizes the stash.
-static bool flash_eligible(const ob_layer_desc* d) {
+static bool flash_eligible(const ob_layer_desc* d, float attn_pdrop = 0.f) {
+  // attention dropout takes the materialized-P path (fused flash dropout is
+  // the follow-up)
+  if (attn_pdrop > 0.f) return false;
   static const bool off = [] {
     const char* e = getenv("OB_BF16_FLASH");
     return e && e[0] == '0';
@@ -241,14 +276,34 @@ extern "C" int64_t ob_layer_param_count(const ob_layer_desc* d) {
   return -1;
 }
 
-extern "C" int ob_layer_create(const ob_layer_desc* d, ob_layer_t* out) {
+static int layer_create(const ob_layer_desc* d, const ob_dropout_desc* drop,
+                        ob_layer_t* out) {
   if (!d || !out) return ob_fail("create: null arg");
   if (d->kind < 0 || d->kind > 2) return ob_fail("create: bad kind");
   if (d->seq_len > 2048)
     return ob_fail("create: seq_len > 2048 unsupported in round 1");
+  if (d->n_slots < 1) return ob_fail("create: n_slots < 1");
+  if (drop) {
+    if (!ob_drop_p_ok(drop->embd_pdrop) || !ob_drop_p_ok(drop->resid_pdrop) ||
+        !ob_drop_p_ok(drop->attn_pdrop))
+      return ob_fail("create_ex: dropout probabilities must be in [0,1)");
+    if (drop->layer_id < 0 || drop->layer_id >= (1 << 24))
+      return ob_fail("create_ex: layer_id out of range");
+  }
   ob_layer* l = new ob_layer();
   l->d = *d;
   l->B = d->max_batch;
+  l->slot_drop.assign(d->n_slots, 0);
+  l->slot_tick.assign(d->n_slots, 0);
+  if (drop) {
+    if (d->kind == OB_KIND_EMBED) l->p_embd = drop->embd_pdrop;
+    if (d->kind == OB_KIND_BLOCK) {
+      l->p_resid = drop->resid_pdrop;
+      l->p_attn = drop->attn_pdrop;
+    }
+    l->layer_id = drop->layer_id;
+    l->seed = drop->seed;
+  }
   const int64_t Bm = d->max_batch, Sq = d->seq_len, H = d->n_embd,
                 nh = d->n_head, V = d->vocab_size;
   const int64_t BS = Bm * Sq, BSH = BS * H;
@@ -263,7 +318,7 @@ extern "C" int ob_layer_create(const ob_layer_desc* d, ob_layer_t* out) {
       l->o_rstd1 = o; o += BS;
       l->o_ln1 = o; o += BSH;
       l->o_qkv = o; o += BS * 3 * H;
-      l->flash = flash_eligible(d);
+      l->flash = flash_eligible(d, l->p_attn);
       l->o_p = o; o += l->flash ? Bm * nh * Sq : Bm * nh * Sq * Sq;
       l->o_attnm = o; o += BSH;
       l->o_hmid = o; o += BSH;
@@ -355,7 +410,38 @@ extern "C" int ob_layer_create(const ob_layer_desc* d, ob_layer_t* out) {
     if (ws_ensure(&g_ws.bsh1, &g_ws.sz_bsh, need)) return 1;
     if (ws_ensure(&g_ws.bsh2, &g_ws.sz_bsh2, need)) return 1;
   }
+  // dropout workspaces (sized in floats; bf16 uses the first half)
+  if (l->p_attn > 0.f) {
+    if (ws_ensure(&g_ws.pd_f, &g_ws.sz_pd_f, Bm * nh * Sq * Sq)) return 1;
+    if (ws_ensure(&g_ws.pd_b, &g_ws.sz_pd_b, Bm * nh * Sq * Sq)) return 1;
+  }
+  if (l->p_resid > 0.f) {
+    if (ws_ensure(&g_ws.dm1, &g_ws.sz_dm1, BSH)) return 1;
+    if (ws_ensure(&g_ws.dm2, &g_ws.sz_dm2, BSH)) return 1;
+  }
   *out = l;
+  return 0;
+}
+
+extern "C" int ob_layer_create(const ob_layer_desc* d, ob_layer_t* out) {
+  return layer_create(d, nullptr, out);
+}
+
+extern "C" int ob_layer_create_ex(const ob_layer_desc* d,
+                                  const ob_dropout_desc* drop,
+                                  ob_layer_t* out) {
+  return layer_create(d, drop, out);
+}
+
+extern "C" int ob_layer_set_training(ob_layer_t l, int on) {
+  if (!l) return ob_fail("set_training: null layer");
+  l->training = on != 0;
+  return 0;
+}
+
+extern "C" int ob_layer_set_dropout_tick(ob_layer_t l, uint64_t tick) {
+  if (!l) return ob_fail("set_dropout_tick: null layer");
+  l->next_tick = tick;
   return 0;
 }
 
@@ -495,6 +581,8 @@ static int block_forward(ob_layer* l, int slot, const float* in, float* out,
   float* st = l->stash + (int64_t)slot * l->slot_stride;
   const float* p = l->params;
   const BlockParams bp = block_params(H);
+  const bool dA = l->slot_drop[slot] && l->p_attn > 0.f;
+  const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;
 
   float* x = st + l->o_x;
   OB_HIP(hipMemcpyAsync(x, in, BS * H * sizeof(float), hipMemcpyDeviceToDevice,
@@ -518,16 +606,31 @@ static int block_forward(ob_layer* l, int slot, const float* in, float* out,
     return 1;
   if (ob_softmax_causal_fwd_f32(P, B * nh, Sq, 1.f / sqrtf((float)hd), stream))
     return 1;
-  // attn_merged[b,:,h*hd:(h+1)*hd] = P[b,h] @ V[b,h]
+  // attention dropout: the stash keeps the undropped P (softmax backward
+  // needs it at dropped positions); the PV GEMM reads Pd = drop(P) from the
+  // forward-only workspace
+  const float* Pv = P;
+  if (dA) {
+    if (ob_drop_scale(drop_key(l, slot, OB_DROP_ATTN, l->p_attn), 0, P,
+                      g_ws.pd_f, B * nh * Sq * Sq, stream))
+      return 1;
+    Pv = g_ws.pd_f;
+  }
+  // attn_merged[b,:,h*hd:(h+1)*hd] = Pd[b,h] @ V[b,h]
   float* am = st + l->o_attnm;
-  if (gemm(0, 0, Sq, hd, Sq, 1.f, P, Sq, nh * Sq * Sq, Sq * Sq, qkv + 2 * H,
+  if (gemm(0, 0, Sq, hd, Sq, 1.f, Pv, Sq, nh * Sq * Sq, Sq * Sq, qkv + 2 * H,
            3 * H, Sq * 3 * H, hd, 0.f, am, H, Sq * H, hd, B, nh, nullptr,
            nullptr, 0, 1, stream))
     return 1;
   // h_mid = attn_merged @ w_attnproj + b + x (residual)
   float* hmid = st + l->o_hmid;
   if (gemm(0, 0, BS, H, H, 1.f, am, H, 0, 0, p + bp.w_attnproj, H, 0, 0, 0.f,
-           hmid, H, 0, 0, 1, 1, p + bp.b_attnproj, x, 0, 1, stream))
+           hmid, H, 0, 0, 1, 1, p + bp.b_attnproj, dR ? nullptr : x, 0, 1,
+           stream))
+    return 1;
+  // residual dropout: the GEMM wrote the biased projection only
+  if (dR && ob_drop_add(drop_key(l, slot, OB_DROP_RESID_ATTN, l->p_resid), 0,
+                        hmid, x, hmid, BS * H, stream))
     return 1;
   float* ln2 = st + l->o_ln2;
   if (ob_layernorm_fwd_f32(hmid, p + bp.ln2_w, p + bp.ln2_b, ln2,
@@ -541,7 +644,11 @@ static int block_forward(ob_layer* l, int slot, const float* in, float* out,
   float* gact = st + l->o_g;
   if (ob_gelu_fwd_f32(u, gact, BS * 4 * H, stream)) return 1;
   if (gemm(0, 0, BS, H, 4 * H, 1.f, gact, 4 * H, 0, 0, p + bp.w_mlpproj, H, 0,
-           0, 0.f, out, H, 0, 0, 1, 1, p + bp.b_mlpproj, hmid, 0, 1, stream))
+           0, 0.f, out, H, 0, 0, 1, 1, p + bp.b_mlpproj, dR ? nullptr : hmid,
+           0, 1, stream))
+    return 1;
+  if (dR && ob_drop_add(drop_key(l, slot, OB_DROP_RESID_MLP, l->p_resid), 0,
+                        out, hmid, out, BS * H, stream))
     return 1;
   return 0;
 }
@@ -635,6 +742,8 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   const float* p = l->params;
   const __bf16* sh = l->shadows;
   const BlockParams bp = block_params(H);
+  const bool dA = l->slot_drop[slot] && l->p_attn > 0.f;
+  const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;
 
   // ln1 reads the input once and also writes its stash copy x
   __bf16* x = (__bf16*)(st + l->o_x);
@@ -676,8 +785,18 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
                 ob_softmax_causal_fwd_bf16(P, B * nh, Sq,
                                            1.f / sqrtf((float)hd), stream)))
       return 1;
+    // attention dropout: stash keeps P, the PV GEMM reads Pd = drop(P) from
+    // the forward-only workspace (create_ex cleared `flash` for p_attn > 0)
+    const __bf16* Pv = P;
+    if (dA) {
+      if (OB_PROF(OB_PF_ELEM, stream,
+                  ob_drop_scale(drop_key(l, slot, OB_DROP_ATTN, l->p_attn), 1,
+                                P, g_ws.pd_f, B * nh * Sq * Sq, stream)))
+        return 1;
+      Pv = (const __bf16*)g_ws.pd_f;
+    }
     if (OB_PROF(OB_PF_ATTN_MAT, stream,
-                gemm_bf(0, 0, Sq, hd, Sq, 1.f, P, Sq, nh * Sq * Sq, Sq * Sq,
+                gemm_bf(0, 0, Sq, hd, Sq, 1.f, Pv, Sq, nh * Sq * Sq, Sq * Sq,
                         qkv + 2 * H, 3 * H, Sq * 3 * H, hd, am, H, Sq * H,
                         hd, B, nh, nullptr, nullptr, 0, 1, stream)))
       return 1;
@@ -685,8 +804,14 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   __bf16* hmid = (__bf16*)(st + l->o_hmid);
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
               gemm_bf(0, 1, BS, H, H, 1.f, am, H, 0, 0, sh + l->sh_ap_t, H,
-                      0, 0, hmid, H, 0, 0, 1, 1, p + bp.b_attnproj, x, 0, 1,
-                      stream)))
+                      0, 0, hmid, H, 0, 0, 1, 1, p + bp.b_attnproj,
+                      dR ? nullptr : x, 0, 1, stream)))
+    return 1;
+  // residual dropout: the GEMM wrote the biased projection only
+  if (dR &&
+      OB_PROF(OB_PF_ELEM, stream,
+              ob_drop_add(drop_key(l, slot, OB_DROP_RESID_ATTN, l->p_resid), 1,
+                          hmid, x, hmid, BS * H, stream)))
     return 1;
   __bf16* ln2 = (__bf16*)(st + l->o_ln2);
   if (OB_PROF(OB_PF_LN, stream,
@@ -707,7 +832,12 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
               gemm_bf(0, 1, BS, H, 4 * H, 1.f, gact, 4 * H, 0, 0,
                       sh + l->sh_mp_t, 4 * H, 0, 0, out, H, 0, 0, 1, 1,
-                      p + bp.b_mlpproj, hmid, 0, 1, stream)))
+                      p + bp.b_mlpproj, dR ? nullptr : hmid, 0, 1, stream)))
+    return 1;
+  if (dR &&
+      OB_PROF(OB_PF_ELEM, stream,
+              ob_drop_add(drop_key(l, slot, OB_DROP_RESID_MLP, l->p_resid), 1,
+                          out, hmid, out, BS * H, stream)))
     return 1;
   return 0;
 }
@@ -773,6 +903,9 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   __bf16* DATT = (__bf16*)g_ws.bsh2;
   __bf16* DQKV = (__bf16*)g_ws.dqkv;
   __bf16* DP = (__bf16*)g_ws.dp;
+  // the masks this slot's forward drew, regenerated from its tick
+  const bool dA = l->slot_drop[slot] && l->p_attn > 0.f;
+  const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;
 
   // The dW family (transposes + atomic GEMMs + the qkv bias colsum) has
   // no consumer inside this call and no effect on the dX chain (the other
@@ -785,13 +918,25 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   OB_SIDE_FENCE(S(stream), g_side.stream);  // entry state (dout ready)
 
   // ---- MLP ----
+  // residual dropout: the projection saw mask*dout; that kernel also takes
+  // the b_mlpproj grad.  The residual branch (ln2 backward) keeps dout.
+  const __bf16* dmlp = dout;
+  if (dR) {
+    if (OB_PROF(OB_PF_ELEM, stream,
+                ob_drop_scale_colsum(
+                    drop_key(l, slot, OB_DROP_RESID_MLP, l->p_resid), 1, dout,
+                    g_ws.dm2, g + bp.b_mlpproj, BS, H, stream)))
+      return 1;
+    dmlp = (const __bf16*)g_ws.dm2;
+    OB_SIDE_FENCE(S(stream), g_side.stream);  // dm2 ready
+  }
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              gemm_bf(0, 1, BS, 4 * H, H, 1.f, dout, H, 0, 0, sh + l->sh_mp,
+              gemm_bf(0, 1, BS, 4 * H, H, 1.f, dmlp, H, 0, 0, sh + l->sh_mp,
                       H, 0, 0, DY4, 4 * H, 0, 0, 1, 1, nullptr, nullptr, 0,
                       1, stream)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DW, side,
-              dw_bf16_ws(gact, 4 * H, dout, H, BS, g + bp.w_mlpproj, H,
+              dw_bf16_ws(gact, 4 * H, dmlp, H, BS, g + bp.w_mlpproj, H,
                          g_ws.s1, g_ws.s2, side)))
     return 1;
   // gelu backward also sums its output columns into the b_fc grad
@@ -816,18 +961,28 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
               ob_layernorm_bwd_res_bf16(hmid, p + bp.ln2_w, st + l->o_mean2,
                                         st + l->o_rstd2, DLN, dout, din,
                                         g + bp.ln2_w, g + bp.ln2_b,
-                                        g + bp.b_mlpproj, g + bp.b_attnproj,
+                                        dR ? nullptr : g + bp.b_mlpproj,
+                                        dR ? nullptr : g + bp.b_attnproj,
                                         BS, H, stream)))
     return 1;
   // ---- attention projection ----
-  OB_SIDE_FENCE(S(stream), g_side.stream);  // din post-ln2-bwd
+  const __bf16* dap = din;
+  if (dR) {
+    if (OB_PROF(OB_PF_ELEM, stream,
+                ob_drop_scale_colsum(
+                    drop_key(l, slot, OB_DROP_RESID_ATTN, l->p_resid), 1, din,
+                    g_ws.dm1, g + bp.b_attnproj, BS, H, stream)))
+      return 1;
+    dap = (const __bf16*)g_ws.dm1;
+  }
+  OB_SIDE_FENCE(S(stream), g_side.stream);  // din post-ln2-bwd (dm1 ready)
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              gemm_bf(0, 1, BS, H, H, 1.f, din, H, 0, 0, sh + l->sh_ap, H, 0,
+              gemm_bf(0, 1, BS, H, H, 1.f, dap, H, 0, 0, sh + l->sh_ap, H, 0,
                       0, DATT, H, 0, 0, 1, 1, nullptr, nullptr, 0, 1,
                       stream)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DW, side,
-              dw_bf16_ws(am, H, din, H, BS, g + bp.w_attnproj, H, g_ws.s1,
+              dw_bf16_ws(am, H, dap, H, BS, g + bp.w_attnproj, H, g_ws.s1,
                          g_ws.s2, side)))
     return 1;
   // din is re-updated by the final ln1 backward: the main stream must
@@ -868,6 +1023,20 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
                         nh * Sq * Sq, Sq * Sq, B, nh, nullptr, nullptr, 0, 1,
                         stream)))
       return 1;
+    // attention dropout: DP holds dPd.  Regenerate Pd for dV, mask dPd into
+    // dP in place, then the softmax backward runs on the stored P.
+    const __bf16* Pv = P;
+    if (dA) {
+      const ob_drop_key ka = drop_key(l, slot, OB_DROP_ATTN, l->p_attn);
+      if (OB_PROF(OB_PF_ELEM, stream,
+                  ob_drop_scale(ka, 1, P, g_ws.pd_b, B * nh * Sq * Sq,
+                                stream)))
+        return 1;
+      if (OB_PROF(OB_PF_ELEM, stream,
+                  ob_drop_scale(ka, 1, DP, DP, B * nh * Sq * Sq, stream)))
+        return 1;
+      Pv = (const __bf16*)g_ws.pd_b;
+    }
     if (OB_PROF(OB_PF_ATTN_MAT, stream,
                 ob_softmax_causal_bwd_bf16(P, DP, B * nh, Sq, stream)))
       return 1;
@@ -884,7 +1053,7 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
                         stream)))
       return 1;
     if (OB_PROF(OB_PF_ATTN_MAT, stream,
-                gemm_bf(1, 0, Sq, hd, Sq, 1.f, P, Sq, nh * Sq * Sq, Sq * Sq,
+                gemm_bf(1, 0, Sq, hd, Sq, 1.f, Pv, Sq, nh * Sq * Sq, Sq * Sq,
                         DATT, H, Sq * H, hd, DQKV + 2 * H, 3 * H, Sq * 3 * H,
                         hd, B, nh, nullptr, nullptr, 0, 1, stream)))
       return 1;
@@ -986,6 +1155,12 @@ extern "C" int ob_layer_forward(ob_layer_t l, int32_t slot, const void* in,
   if (!l) return ob_fail("forward: null layer");
   if (!l->params) return ob_fail("forward: params not bound");
   if (slot < 0 || slot >= l->d.n_slots) return ob_fail("forward: bad slot");
+  // dropout bookkeeping: this slot's backward regenerates the masks from
+  // the tick recorded here, never from "the latest"
+  const bool drop = l->training && has_dropout(l);
+  l->slot_drop[slot] = drop ? 1 : 0;
+  l->slot_tick[slot] = l->next_tick;
+  if (drop) l->next_tick++;
   switch (l->d.kind) {
     case OB_KIND_EMBED: {
       const int64_t Sq = l->d.seq_len, H = l->d.n_embd, V = l->d.vocab_size;
@@ -993,6 +1168,12 @@ extern "C" int ob_layer_forward(ob_layer_t l, int32_t slot, const void* in,
       int64_t* ids = l->ids + (int64_t)slot * (int64_t)l->d.max_batch * Sq;
       OB_HIP(hipMemcpyAsync(ids, in, BS * sizeof(int64_t),
                             hipMemcpyDeviceToDevice, S(stream)));
+      if (drop)
+        return OB_PROF(OB_PF_ELEM, stream,
+                       ob_embed_fwd_drop(
+                           drop_key(l, slot, OB_DROP_EMBD, l->p_embd),
+                           l->d.dtype == 1, ids, l->params, l->params + V * H,
+                           out, l->B, Sq, H, stream));
       if (l->d.dtype == 1)
         return OB_PROF(OB_PF_ELEM, stream,
                        ob_embed_fwd_bf16(ids, l->params, l->params + V * H,
@@ -1046,21 +1227,34 @@ static int block_backward(ob_layer* l, int slot, const float* dout, float* din,
   float* DATT = g_ws.bsh2;  // [BS,H]
   float* DQKV = g_ws.dqkv;  // [BS,3H]
   float* DP = g_ws.dp;      // [B*nh,S,S]
+  // the masks this slot's forward drew, regenerated from its tick
+  const bool dA = l->slot_drop[slot] && l->p_attn > 0.f;
+  const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;
 
   // din starts as d(h_mid) accumulator = dout (residual skip)
   OB_HIP(hipMemcpyAsync(din, dout, BS * H * sizeof(float),
                         hipMemcpyDeviceToDevice, S(stream)));
   // ---- MLP backward ----
+  // residual dropout: the projection saw dm = mask*dout (the kernel also
+  // takes db = colsum(dm)); the residual skip above keeps dout itself
+  const float* dmlp = dout;
+  if (dR) {
+    if (ob_drop_scale_colsum(drop_key(l, slot, OB_DROP_RESID_MLP, l->p_resid),
+                             0, dout, g_ws.dm2, g + bp.b_mlpproj, BS, H,
+                             stream))
+      return 1;
+    dmlp = g_ws.dm2;
+  }
   // dg = dout @ w_mlpproj^T
-  if (gemm(0, 1, BS, 4 * H, H, 1.f, dout, H, 0, 0, p + bp.w_mlpproj, H, 0, 0,
+  if (gemm(0, 1, BS, 4 * H, H, 1.f, dmlp, H, 0, 0, p + bp.w_mlpproj, H, 0, 0,
            0.f, DY4, 4 * H, 0, 0, 1, 1, nullptr, nullptr, 0, 1, stream))
     return 1;
   // dW_mlpproj += g^T @ dout ; db += colsum(dout)
-  if (gemm(1, 0, 4 * H, H, BS, 1.f, gact, 4 * H, 0, 0, dout, H, 0, 0, 1.f,
+  if (gemm(1, 0, 4 * H, H, BS, 1.f, gact, 4 * H, 0, 0, dmlp, H, 0, 0, 1.f,
            g + bp.w_mlpproj, H, 0, 0, 1, 1, nullptr, nullptr, 1,
            pick_splitk(4 * H, H, BS), stream))
     return 1;
-  if (ob_colsum_f32(dout, g + bp.b_mlpproj, BS, H, stream)) return 1;
+  if (!dR && ob_colsum_f32(dout, g + bp.b_mlpproj, BS, H, stream)) return 1;
   // du = dg * gelu'(u)   (in place on DY4)
   if (ob_gelu_bwd_f32(u, DY4, DY4, BS * 4 * H, stream)) return 1;
   // dW_fc += ln2^T @ du ; db_fc += colsum(du)
@@ -1079,20 +1273,37 @@ static int block_backward(ob_layer* l, int slot, const float* dout, float* din,
                            g + bp.ln2_b, BS, H, 1, stream))
     return 1;
   // ---- attention projection backward (din now = d_hmid) ----
-  if (gemm_dx_splitk(1, BS, H, H, 1.f, din, H, p + bp.w_attnproj, H, DATT,
+  const float* dap = din;
+  if (dR) {
+    if (ob_drop_scale_colsum(drop_key(l, slot, OB_DROP_RESID_ATTN, l->p_resid),
+                             0, din, g_ws.dm1, g + bp.b_attnproj, BS, H,
+                             stream))
+      return 1;
+    dap = g_ws.dm1;
+  }
+  if (gemm_dx_splitk(1, BS, H, H, 1.f, dap, H, p + bp.w_attnproj, H, DATT,
                      H, stream))
     return 1;
-  if (gemm(1, 0, H, H, BS, 1.f, am, H, 0, 0, din, H, 0, 0, 1.f,
+  if (gemm(1, 0, H, H, BS, 1.f, am, H, 0, 0, dap, H, 0, 0, 1.f,
            g + bp.w_attnproj, H, 0, 0, 1, 1, nullptr, nullptr, 1,
            pick_splitk(H, H, BS), stream))
     return 1;
-  if (ob_colsum_f32(din, g + bp.b_attnproj, BS, H, stream)) return 1;
+  if (!dR && ob_colsum_f32(din, g + bp.b_attnproj, BS, H, stream)) return 1;
   // ---- attention core backward ----
   // dP = dO @ V^T
   if (gemm(0, 1, Sq, Sq, hd, 1.f, DATT, H, Sq * H, hd, qkv + 2 * H, 3 * H,
            Sq * 3 * H, hd, 0.f, DP, Sq, nh * Sq * Sq, Sq * Sq, B, nh, nullptr,
            nullptr, 0, 1, stream))
     return 1;
+  // attention dropout: DP holds dPd.  Regenerate Pd for dV, mask dPd into
+  // dP in place; the softmax backward then runs on the stored P.
+  const float* Pv = P;
+  if (dA) {
+    const ob_drop_key ka = drop_key(l, slot, OB_DROP_ATTN, l->p_attn);
+    if (ob_drop_scale(ka, 0, P, g_ws.pd_b, B * nh * Sq * Sq, stream)) return 1;
+    if (ob_drop_scale(ka, 0, DP, DP, B * nh * Sq * Sq, stream)) return 1;
+    Pv = g_ws.pd_b;
+  }
   // dS = softmax_bwd(P, dP)  in place on DP
   if (ob_softmax_causal_bwd_f32(P, DP, B * nh, Sq, stream)) return 1;
   // dQ = scale * dS @ K
@@ -1105,8 +1316,8 @@ static int block_backward(ob_layer* l, int slot, const float* dout, float* din,
            Sq * 3 * H, hd, 0.f, DQKV + H, 3 * H, Sq * 3 * H, hd, B, nh,
            nullptr, nullptr, 0, 1, stream))
     return 1;
-  // dV = P^T @ dO
-  if (gemm(1, 0, Sq, hd, Sq, 1.f, P, Sq, nh * Sq * Sq, Sq * Sq, DATT, H,
+  // dV = Pd^T @ dO
+  if (gemm(1, 0, Sq, hd, Sq, 1.f, Pv, Sq, nh * Sq * Sq, Sq * Sq, DATT, H,
            Sq * H, hd, 0.f, DQKV + 2 * H, 3 * H, Sq * 3 * H, hd, B, nh,
            nullptr, nullptr, 0, 1, stream))
     return 1;
@@ -1165,6 +1376,12 @@ extern "C" int ob_layer_backward(ob_layer_t l, int32_t slot, const void* dout,
     case OB_KIND_EMBED: {
       const int64_t Sq = l->d.seq_len, H = l->d.n_embd, V = l->d.vocab_size;
       int64_t* ids = l->ids + (int64_t)slot * (int64_t)l->d.max_batch * Sq;
+      if (l->slot_drop[slot])
+        return OB_PROF(OB_PF_ELEM, stream,
+                       ob_embed_bwd_drop(
+                           drop_key(l, slot, OB_DROP_EMBD, l->p_embd),
+                           l->d.dtype == 1, ids, dout, l->grads,
+                           l->grads + V * H, l->B, Sq, H, stream));
       if (l->d.dtype == 1)
         return OB_PROF(OB_PF_ELEM, stream,
                        ob_embed_bwd_bf16(ids, dout, l->grads,

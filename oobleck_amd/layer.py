@@ -12,7 +12,7 @@ import ctypes
 import torch
 import torch.distributed
 
-from ._ext import ObLayerDesc, check, get_ext
+from ._ext import ObDropoutDesc, ObLayerDesc, check, get_ext
 from .config import ModelConfig
 from .params import init_layer_params
 
@@ -48,7 +48,13 @@ class Layer:
                  seq_len: int, n_slots: int, device: torch.device,
                  process_group: torch.distributed.ProcessGroup | None = None,
                  init_style: str = "gpt2", seed: int = 42,
-                 dtype: str = "f32"):
+                 dtype: str = "f32", embd_pdrop: float | None = None,
+                 resid_pdrop: float | None = None,
+                 attn_pdrop: float | None = None, dropout_seed: int = 0):
+        """Dropout: the three probabilities default to the ModelConfig's;
+        with all of them 0 the layer is created by ob_layer_create and is
+        exactly the dropout-free layer.  Masks are stateless functions of
+        (dropout_seed, layer_id, site, tick, element) — see forward_slot."""
         self.layer_id = layer_id
         self.cfg = cfg
         self.kind = cfg.layer_kind(layer_id)
@@ -69,9 +75,25 @@ class Layer:
         if process_group is not None and torch.distributed.is_initialized():
             group_size = torch.distributed.get_world_size(process_group)
         handle = ctypes.c_void_p()
-        check(ext.ob_layer_create(ctypes.byref(self._desc),
-                                  ctypes.byref(handle)), "layer_create")
+        pdrops = [getattr(cfg, name, 0.0) if v is None else v
+                  for name, v in (("embd_pdrop", embd_pdrop),
+                                  ("resid_pdrop", resid_pdrop),
+                                  ("attn_pdrop", attn_pdrop))]
+        self.has_dropout = any(p != 0 for p in pdrops)
+        if self.has_dropout:
+            self._drop = ObDropoutDesc(
+                embd_pdrop=pdrops[0], resid_pdrop=pdrops[1],
+                attn_pdrop=pdrops[2], layer_id=layer_id,
+                seed=dropout_seed & 0xFFFFFFFFFFFFFFFF)
+            check(ext.ob_layer_create_ex(ctypes.byref(self._desc),
+                                         ctypes.byref(self._drop),
+                                         ctypes.byref(handle)),
+                  "layer_create_ex")
+        else:
+            check(ext.ob_layer_create(ctypes.byref(self._desc),
+                                      ctypes.byref(handle)), "layer_create")
         self._h = handle
+        self.training = True
         self._sharded = None
         if group_size > 1:
             from .sharding import ShardedFlatParam
@@ -118,10 +140,28 @@ class Layer:
                   f"refresh_weights layer {self.layer_id}")
             self._shadows_stale = False
 
+    def train(self) -> None:
+        """Training mode (the default): dropout masks are drawn."""
+        check(get_ext().ob_layer_set_training(self._h, 1), "set_training")
+        self.training = True
+
+    def eval(self) -> None:
+        """Dropout inert: forwards run the dropout-free path."""
+        check(get_ext().ob_layer_set_training(self._h, 0), "set_training")
+        self.training = False
+
     def forward_slot(self, slot: int, x: torch.Tensor, out: torch.Tensor,
-                     labels: torch.Tensor | None = None) -> None:
+                     labels: torch.Tensor | None = None,
+                     tick: int | None = None) -> None:
+        """tick: the dropout tick of this forward (every layer of the model
+        should see the same tick for the same microbatch).  None continues
+        from the layer's own counter, which post-increments per training
+        forward.  The backward of `slot` regenerates this forward's masks."""
         if self._sharded is not None:
             self._unshard()  # pre_forward_hook (layer.py:147-153)
+        if tick is not None and self.has_dropout:
+            check(get_ext().ob_layer_set_dropout_tick(self._h, tick),
+                  "set_dropout_tick")
         check(get_ext().ob_layer_forward(self._h, slot, _ptr(x), _ptr(out),
                                          _ptr(labels), _stream_ptr()),
               f"forward layer {self.layer_id}")

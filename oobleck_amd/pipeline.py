@@ -66,6 +66,13 @@ class PipelineExecution:
         self.total_loss: torch.Tensor | None = None
         self._optimizer = optimizer
         self._lr_scheduler = lr_scheduler
+        # dropout tick = optimizer step * microbatches + microbatch index:
+        # a function of training progress only, never of call history, so a
+        # pipeline rebuilt by reconfiguration continues the same mask
+        # sequence from its optimizer's step count alone
+        self._any_dropout = any(getattr(l, "has_dropout", False)
+                                for l in layers)
+        self._mb_fwd = 0  # forwards issued in the current train() call
         # a clipping optimizer needs the norm over the WHOLE pipeline, not
         # this stage: hand it the pipeline-wide group, or refuse loudly
         # (test doubles without max_grad_norm pass through untouched)
@@ -204,6 +211,10 @@ class PipelineExecution:
         x, labels = self.pipeline.pipe_buffers["inputs"][buffer_id]
         batch = x.shape[0]
         n = len(self._layers)
+        tick = None
+        if self._any_dropout:
+            tick = self.dropout_tick(self._mb_fwd)
+        self._mb_fwd += 1
         for i, layer in enumerate(self._layers):
             layer.set_batch(batch)
             if layer.kind == KIND_FINAL:
@@ -212,7 +223,10 @@ class PipelineExecution:
                     out = torch.zeros(1, dtype=torch.float32,
                                       device=self.pipeline.device)
                     self._loss_bufs[buffer_id] = out
-                layer.forward_slot(buffer_id, x, out, labels)
+                if tick is None:
+                    layer.forward_slot(buffer_id, x, out, labels)
+                else:
+                    layer.forward_slot(buffer_id, x, out, labels, tick=tick)
             else:
                 if i == n - 1:
                     out = self._out_bufs.get(buffer_id)
@@ -224,7 +238,10 @@ class PipelineExecution:
                     out = out[:batch]
                 else:
                     out = self._get_tmp(i % 2, batch)
-                layer.forward_slot(buffer_id, x, out)
+                if tick is None:
+                    layer.forward_slot(buffer_id, x, out)
+                else:
+                    layer.forward_slot(buffer_id, x, out, tick=tick)
             x = out
 
         if self.pipeline.is_last_stage():
@@ -234,6 +251,11 @@ class PipelineExecution:
             self.total_loss += self._loss.detach()
         else:
             self.pipeline.pipe_buffers["outputs"][buffer_id] = (x, labels)
+
+    def dropout_tick(self, microbatch: int) -> int:
+        """Tick of microbatch `microbatch` of the step being computed."""
+        step = int(getattr(self._optimizer, "step_count", 0))
+        return step * self.pipeline.num_microbatches + microbatch
 
     def backward_pass(self, buffer_id: int) -> None:
         if self._overlap:
@@ -404,6 +426,15 @@ class OobleckPipeline:
         self.execution: PipelineExecution | None = None
         self.communication: PipelineCommunication | None = None
 
+    @property
+    def dropout_seed(self) -> int:
+        """The seed this pipeline's layer factory passes to
+        Layer(dropout_seed=...): TrainingConfig.dropout_seed with the pipeline
+        id folded in, so data-parallel replicas draw different masks while
+        every stage of one pipeline agrees (64-bit golden-ratio stride)."""
+        return (self.training_cfg.dropout_seed +
+                self._pipeline_id * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+
     # -- process-group setup (all ranks co-call new_group) -------------------
     def initialize_distributed_fsdp(self) -> None:
         # per-layer groups (reference pipeline.py:565-580)
@@ -495,6 +526,7 @@ class OobleckPipeline:
         import os
         import sys
         trace = os.environ.get("OB_TRACE_SCHED", "0") == "1"
+        self.execution._mb_fwd = 0
         if getattr(self.execution, "_overlap", False):
             # the optimizer / DP all-reduce / zero_grads of the previous
             # step ran on the default stream AFTER the epoch join; the
