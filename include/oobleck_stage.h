@@ -299,6 +299,21 @@ int ob_gemm_bf16(int transA, int transB, int64_t M, int64_t N, int64_t K,
                  const void* bias, const void* residual, int out_kind,
                  int splitk, void* stream);
 
+/* Fused causal flash attention on packed bf16 qkv [B, Sq, 3H] (head_dim 64,
+ * Sq % 128 == 0) without transposed operand copies: the kernels read the
+ * column-major MFMA operands from their row-major LDS tiles.
+ * fwd: O bf16 [B, Sq, H], lse fp32 [B*nh, Sq].
+ * bwd: D fp32 [B*nh, Sq] = rowsum(dO * O); dqkv bf16 [B, Sq, 3H];
+ * dbias_qkv: fp32 [3H] or null; when given, the column sums of dqkv (from
+ * the fp32 accumulators, before bf16 rounding) are atomically added. */
+int ob_flash_fwd_nt_bf16(const void* qkv, void* O, void* lse, int64_t B,
+                         int64_t Sq, int64_t H, int64_t nh, float scale,
+                         void* stream);
+int ob_flash_bwd_nt_bf16(const void* qkv, const void* dO, const void* lse,
+                         const void* D, void* dqkv, void* dbias_qkv,
+                         int64_t B, int64_t Sq, int64_t H, int64_t nh,
+                         float scale, void* stream);
+
 /* dtype casts (weight shadows / activation conversion). */
 int ob_f32_to_bf16(const void* x, void* y, int64_t n, void* stream);
 int ob_f32_to_bf16_t(const void* x, void* y, int64_t rows, int64_t cols,

@@ -145,6 +145,10 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.ob_flash_dsum_bf16.argtypes = [vp, vp, vp, i64, i64, i64, i64, vp]
     lib.ob_flash_bwd_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64,
                                       i64, i64, i64, f32, vp]
+    lib.ob_flash_fwd_nt_bf16.argtypes = [vp, vp, vp, i64, i64, i64, i64,
+                                         f32, vp]
+    lib.ob_flash_bwd_nt_bf16.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64,
+                                         i64, i64, f32, vp]
     return lib
 
 

@@ -3791,6 +3791,527 @@ extern "C" int ob_flash_bwd_bf16(const void* qkv, const void* QT,
 }
 
 // ---------------------------------------------------------------------------
+// "nt" flash kernels: no materialized V^T / Q^T / K^T / dO^T.  Each is the
+// production kernel above with ONE change: the MFMA B operand that used to
+// come from a transposed copy is read column-wise from the row-major LDS
+// tile the kernel stages anyway, with gfx950's ds_read_b64_tr_b16 (a
+// 16-lane group reads a 4-row x 16-column block and receives it
+// column-major).  MFMA order and operand values are unchanged, so the
+// outputs are bit-identical to ob_flash_fwd_bf16 / ob_flash_bwd_bf16.
+//
+// LDS image of a [rows][64] bf16 tile (128-byte rows, 16-byte chunks):
+//   chunk ch of row r lives at chunk slot  ch ^ key(r),
+//   key(r) = ((r>>1)&1)<<2 | ((r>>2)&3).
+// Bank = (byte/4) % 64, i.e. 256 B = two rows per bank sweep.
+//  * transposed read, one 32-lane half = rows r0..r0+3 (r0 % 4 == 0) x one
+//    aligned group of 4 chunks: rows r and r+1 differ in byte bit 7, rows
+//    r and r+2 differ in key bit 2 (the other 64 B of the row); the low
+//    key bits only permute chunks inside the group -> 16 distinct 16-B
+//    slots of the 256-B sweep, conflict-free.  (The production image,
+//    key = r&7, puts rows r and r+2 in the same slots: 2-way.)
+//  * ds_read_b128 row read (lane il -> row il, one chunk index per half):
+//    its 16-lane groups {0-3,12-15,20-27} / {4-11,16-19,28-31} hold 8 even
+//    and 8 odd rows each; over either set key(r) takes all 8 values ->
+//    conflict-free (key = r&7 repeats every 8 rows: 2-way in these groups).
+// The transposed read needs EXEC all ones and 8-byte-aligned lane
+// addresses: every call below sits under wave-uniform control only.
+// ---------------------------------------------------------------------------
+using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
+
+__device__ __forceinline__ int nt_key(int row) {
+  return (((row >> 1) & 1) << 2) | ((row >> 2) & 3);
+}
+// element offset of 16-byte chunk `ch` (0..7) of row `row`
+__device__ __forceinline__ int nt_off(int row, int ch) {
+  return row * 64 + ((ch ^ nt_key(row)) << 3);
+}
+// B fragment (32x32x16, k-slab rows r0..r0+7, r0 % 8 == 0) of column
+// 32*dhalf + (lane&31) from the row-major tile: two transposed reads of
+// the 4x16 blocks at rows r0 / r0+4, first column 32*dhalf + 16*(il>>4).
+// Lane i = lane&15 supplies row (i>>2), columns 4*(i&3)..+3 of its block.
+__device__ __forceinline__ bf16x8 nt_tr_frag(const __bf16* tile, int lane,
+                                             int r0, int dhalf) {
+  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+  const int i = lane & 15;
+  const int row = r0 + (i >> 2);
+  const int ch = 4 * dhalf + 2 * ((lane >> 4) & 1) + ((i >> 1) & 1);
+  const int sub = 4 * (i & 1);
+  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+      (lds_bf16x4*)(tile + nt_off(row, ch) + sub));
+  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+      (lds_bf16x4*)(tile + nt_off(row + 4, ch) + sub));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// k_flash_fwd_bf16_v4 with vbuf staged from V rows (like kbuf from K rows)
+__global__ __launch_bounds__(256, 3) void k_flash_fwd_nt(
+    const __bf16* __restrict__ qkv, __bf16* __restrict__ Obase,
+    float* __restrict__ lse, int Sq, int H, int nh, float scale) {
+  __shared__ __attribute__((aligned(16))) __bf16 kbuf[2][64 * 64];
+  __shared__ __attribute__((aligned(16))) __bf16 vbuf[2][64 * 64];
+  __shared__ float bcast[128];
+  const int z = blockIdx.z;
+  const int b = z / nh, h = z % nh;
+  const int64_t qoff = (int64_t)b * Sq * 3 * H + h * 64;
+  const __bf16* Qp = qkv + qoff;
+  const __bf16* Kp = Qp + H;
+  const __bf16* Vp = Qp + 2 * H;
+  __bf16* Op = Obase + (int64_t)b * Sq * H + h * 64;
+  float* lsep = lse + (int64_t)z * Sq;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int w = tid >> 6;
+  const int il = lane & 31, kh = lane >> 5;
+  const int q0b = blockIdx.x * 128;
+  const int q0 = q0b + w * 32;
+  const int myq = q0 + il;
+
+  // staging: thread covers chunks tid and tid+256 of the 512-slot tile
+  const int sr0 = tid >> 3, sr1 = sr0 + 32, sc = tid & 7;
+  const int so0 = nt_off(sr0, sc), so1 = nt_off(sr1, sc);
+  auto stage = [&](int buf, int kv0) {
+    *reinterpret_cast<bf16x8*>(&kbuf[buf][so0]) =
+        *reinterpret_cast<const bf16x8*>(
+            Kp + (int64_t)(kv0 + sr0) * 3 * H + sc * 8);
+    *reinterpret_cast<bf16x8*>(&kbuf[buf][so1]) =
+        *reinterpret_cast<const bf16x8*>(
+            Kp + (int64_t)(kv0 + sr1) * 3 * H + sc * 8);
+    *reinterpret_cast<bf16x8*>(&vbuf[buf][so0]) =
+        *reinterpret_cast<const bf16x8*>(
+            Vp + (int64_t)(kv0 + sr0) * 3 * H + sc * 8);
+    *reinterpret_cast<bf16x8*>(&vbuf[buf][so1]) =
+        *reinterpret_cast<const bf16x8*>(
+            Vp + (int64_t)(kv0 + sr1) * 3 * H + sc * 8);
+  };
+
+  bf16x8 qf[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+    qf[s] = *reinterpret_cast<const bf16x8*>(
+        Qp + (int64_t)myq * 3 * H + s * 16 + kh * 8);
+
+  const int ntiles = (q0b + 128) / 64;
+  stage(0, 0);
+  __syncthreads();
+
+  f32x16 o0 = {}, o1 = {};
+  float m = -INFINITY, l = 0.f;
+  for (int kvt = 0; kvt < ntiles; ++kvt) {
+    const int kv0 = kvt * 64;
+    if (kvt + 1 < ntiles) stage((kvt + 1) & 1, kv0 + 64);
+    const bool active = kv0 <= q0 + 31;
+    if (active) {
+      const __bf16* kb = kbuf[kvt & 1];
+      const __bf16* vb = vbuf[kvt & 1];
+      f32x16 sacc0 = {}, sacc1 = {};
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int ch = (s * 2 + kh);
+        const bf16x8 ka =
+            *reinterpret_cast<const bf16x8*>(&kb[nt_off(il, ch)]);
+        const bf16x8 kb2 =
+            *reinterpret_cast<const bf16x8*>(&kb[nt_off(32 + il, ch)]);
+        sacc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qf[s], sacc0, 0,
+                                                        0, 0);
+        sacc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kb2, qf[s], sacc1,
+                                                        0, 0, 0);
+      }
+      float sv[32];
+      if (kv0 + 63 < q0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          sv[r] = sacc0[r] * scale;
+          sv[16 + r] = sacc1[r] * scale;
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kvr = kv0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+          sv[r] = (kvr <= myq) ? sacc0[r] * scale : -INFINITY;
+          sv[16 + r] = (kvr + 32 <= myq) ? sacc1[r] * scale : -INFINITY;
+        }
+      }
+      float mx[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        mx[j] = fmaxf(fmaxf(sv[j], sv[8 + j]),
+                      fmaxf(sv[16 + j], sv[24 + j]));
+      float mt = fmaxf(fmaxf(fmaxf(mx[0], mx[1]), fmaxf(mx[2], mx[3])),
+                       fmaxf(fmaxf(mx[4], mx[5]), fmaxf(mx[6], mx[7])));
+      mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+      const bool rescale = !__all(mt - m <= 8.f);
+      if (rescale) {
+        const float mnew = fmaxf(m, mt);
+        const float af = __expf(m - mnew);
+        m = mnew;
+        if (kh == 0) bcast[w * 32 + il] = af;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const float a = bcast[w * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh];
+          o0[r] *= a;
+          o1[r] *= a;
+        }
+        l *= af;
+      }
+      float ps[8] = {};
+#pragma unroll
+      for (int r = 0; r < 32; ++r) {
+        sv[r] = (sv[r] == -INFINITY) ? 0.f : __expf(sv[r] - m);
+        ps[r & 7] += sv[r];
+      }
+      float psum = ((ps[0] + ps[1]) + (ps[2] + ps[3])) +
+                   ((ps[4] + ps[5]) + (ps[6] + ps[7]));
+      psum += __shfl_xor(psum, 32, 64);
+      l += psum;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const bf16x8 pa = bf_dance(sv + t * 8);
+        // B[k = kv 16t+8kh..+7][n = d]: columns of the row-major V tile
+        const bf16x8 v0f = nt_tr_frag(vb, lane, t * 16 + kh * 8, 0);
+        const bf16x8 v1f = nt_tr_frag(vb, lane, t * 16 + kh * 8, 1);
+        o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, v0f, o0, 0, 0, 0);
+        o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa, v1f, o1, 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+
+  if (kh == 0) {
+    bcast[w * 32 + il] = 1.f / l;
+    lsep[myq] = m + __logf(l);
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
+    const float inv = bcast[w * 32 + row];
+    Op[(int64_t)(q0 + row) * H + il] = (__bf16)(o0[r] * inv);
+    Op[(int64_t)(q0 + row) * H + 32 + il] = (__bf16)(o1[r] * inv);
+  }
+}
+
+extern "C" int ob_flash_fwd_nt_bf16(const void* qkv, void* O, void* lse,
+                                    int64_t B, int64_t Sq, int64_t H,
+                                    int64_t nh, float scale, void* stream) {
+  if (H / nh != 64) return ob_fail("flash_fwd_nt: head_dim must be 64");
+  if (Sq % 128) return ob_fail("flash_fwd_nt: S must be a multiple of 128");
+  dim3 grid((unsigned)(Sq / 128), 1, (unsigned)(B * nh));
+  k_flash_fwd_nt<<<grid, 256, 0, S(stream)>>>(
+      (const __bf16*)qkv, (__bf16*)O, (float*)lse, (int)Sq, (int)H, (int)nh,
+      scale);
+  OB_LAUNCH_CHECK();
+  return 0;
+}
+
+// k_flash_bwd_dkdv_s with the dV/dK B operands (dO^T for role 0, Q^T for
+// role 1) read column-wise from the staged obuf/qbuf tile of the current
+// q-tile.  The reads stay BEFORE the iteration's barrier: after it a fast
+// wave already stages tile qt+2 into this buffer.
+// dbias (fp32 [3H], may be null): += column sums of this block's dK and dV
+// tiles, taken from the fp32 accumulators after `scale`, before rounding.
+__global__ __launch_bounds__(256, 3) void k_flash_bwd_dkdv_nt(
+    const __bf16* __restrict__ qkv, const __bf16* __restrict__ dO,
+    const float* __restrict__ lse, const float* __restrict__ D,
+    __bf16* __restrict__ dqkv, float* __restrict__ dbias, int Sq, int H,
+    int nh, float scale) {
+  __shared__ float xch[2][2][32 * 32];  // [buffer][pair][P tile]
+  __shared__ __attribute__((aligned(16))) __bf16 qbuf[2][32 * 64];
+  __shared__ __attribute__((aligned(16))) __bf16 obuf[2][32 * 64];
+  __shared__ float red[4 * 64];
+  const int z = blockIdx.z;
+  const int b = z / nh, h = z % nh;
+  const int64_t base = (int64_t)b * Sq * 3 * H + h * 64;
+  const __bf16* Qp = qkv + base;
+  const __bf16* Kp = Qp + H;
+  const __bf16* Vp = Qp + 2 * H;
+  const __bf16* dOp = dO + (int64_t)b * Sq * H + h * 64;
+  const float* lsep = lse + (int64_t)z * Sq;
+  const float* Dp = D + (int64_t)z * Sq;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int w = tid >> 6;
+  const int pair = w >> 1, role = w & 1;
+  const int il = lane & 31, kh = lane >> 5;
+  const int kv0 = blockIdx.x * 64 + pair * 32;
+  const int mykv = kv0 + il;
+
+  const __bf16* KV = role ? Vp : Kp;
+  bf16x8 of[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+    of[s] = *reinterpret_cast<const bf16x8*>(
+        KV + (int64_t)mykv * 3 * H + s * 16 + kh * 8);
+
+  const int srow = tid >> 3, schunk = tid & 7;
+  const int so = nt_off(srow, schunk);
+  auto stage = [&](int buf, int q0s) {
+    *reinterpret_cast<bf16x8*>(&qbuf[buf][so]) =
+        *reinterpret_cast<const bf16x8*>(
+            Qp + (int64_t)(q0s + srow) * 3 * H + schunk * 8);
+    *reinterpret_cast<bf16x8*>(&obuf[buf][so]) =
+        *reinterpret_cast<const bf16x8*>(
+            dOp + (int64_t)(q0s + srow) * H + schunk * 8);
+  };
+
+  f32x16 acc0 = {}, acc1 = {};  // role 0: dV d-halves; role 1: dK d-halves
+  const int nqt = Sq / 32;
+  const int qt0 = (blockIdx.x * 64) / 32;
+  stage(qt0 & 1, qt0 * 32);
+  __syncthreads();
+
+  for (int qt = qt0; qt < nqt; ++qt) {
+    const int q0 = qt * 32;
+    if (qt + 1 < nqt) stage((qt + 1) & 1, q0 + 32);
+    // own tile's A image, and the B image: role 0 multiplies P^T by dO,
+    // role 1 dS^T by Q
+    const __bf16* ab = role ? obuf[qt & 1] : qbuf[qt & 1];
+    const __bf16* bb = role ? qbuf[qt & 1] : obuf[qt & 1];
+    // B-operands early (before the barrier): both d-halves, k = q rows
+    const bf16x8 b00 = nt_tr_frag(bb, lane, kh * 8, 0);
+    const bf16x8 b01 = nt_tr_frag(bb, lane, kh * 8, 1);
+    const bf16x8 b10 = nt_tr_frag(bb, lane, 16 + kh * 8, 0);
+    const bf16x8 b11 = nt_tr_frag(bb, lane, 16 + kh * 8, 1);
+    // own tile: S (role 0, A = Q rows) or dP (role 1, A = dO rows)
+    f32x16 own = {};
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int ch = s * 2 + kh;
+      const bf16x8 af =
+          *reinterpret_cast<const bf16x8*>(&ab[nt_off(il, ch)]);
+      own = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, of[s], own, 0, 0,
+                                                    0);
+    }
+    float pv[16];
+    float* ptile = xch[qt & 1][pair];
+    if (role == 0) {
+      const float lse_t = lsep[q0 + il];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int qoff = acc_row(r, kh);
+        const bool ok = q0 + qoff >= mykv;
+        const float lse_q = __shfl(lse_t, qoff, 64);
+        pv[r] = ok ? __expf(own[r] * scale - lse_q) : 0.f;
+        ptile[qoff * 32 + il] = pv[r];
+      }
+    }
+    __syncthreads();
+    if (role == 1) {
+      const float d_t = Dp[q0 + il];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int qoff = acc_row(r, kh);
+        const float d_q = __shfl(d_t, qoff, 64);
+        // dS = P * (dP - D); masked entries have P == 0 already
+        pv[r] = ptile[qoff * 32 + il] * (own[r] - d_q);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const bf16x8 a = bf_dance(pv + t * 8);
+      const bf16x8 bl = t ? b10 : b00;
+      const bf16x8 bh = t ? b11 : b01;
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bl, acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bh, acc1, 0, 0, 0);
+    }
+  }
+
+  __bf16* outp = dqkv + base + (role ? H : 2 * H);  // dK or dV slice
+  const float os = role ? scale : 1.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int kv = kv0 + acc_row(r, kh);
+    outp[(int64_t)kv * 3 * H + il] = (__bf16)(os * acc0[r]);
+    outp[(int64_t)kv * 3 * H + 32 + il] = (__bf16)(os * acc1[r]);
+  }
+  if (dbias) {  // kernel-uniform
+    float c0 = 0.f, c1 = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      c0 += os * acc0[r];
+      c1 += os * acc1[r];
+    }
+    c0 += __shfl_xor(c0, 32, 64);
+    c1 += __shfl_xor(c1, 32, 64);
+    if (kh == 0) {
+      red[w * 64 + il] = c0;
+      red[w * 64 + 32 + il] = c1;
+    }
+    __syncthreads();
+    if (tid < 128) {
+      // waves 0/2 hold dV (role 0), waves 1/3 dK (role 1)
+      const int rl = tid >> 6, c = tid & 63;
+      atomicAdd(dbias + (rl ? H : 2 * H) + h * 64 + c,
+                red[rl * 64 + c] + red[(2 + rl) * 64 + c]);
+    }
+  }
+}
+
+// k_flash_bwd_dq_v3 without the K^T tile: kt0/kt1 are column reads of the
+// K tile the S chains already use (LDS 48 KB -> 32 KB).
+// dbias (fp32 [3H], may be null): += column sums of this block's dQ tile.
+// Bound 3 (not the parent's 2): the parent compiles to 167 VGPRs and so
+// already runs 3 waves/SIMD; this body came to 169 under bound 2, which
+// would have dropped it to 2.
+__global__ __launch_bounds__(256, 3) void k_flash_bwd_dq_nt(
+    const __bf16* __restrict__ qkv, const __bf16* __restrict__ dO,
+    const float* __restrict__ lse, const float* __restrict__ D,
+    __bf16* __restrict__ dqkv, float* __restrict__ dbias, int Sq, int H,
+    int nh, float scale) {
+  __shared__ __attribute__((aligned(16))) __bf16 kbuf[2][64 * 64];
+  __shared__ __attribute__((aligned(16))) __bf16 vbuf[2][64 * 64];
+  __shared__ float red[4 * 64];
+  const int z = blockIdx.z;
+  const int b = z / nh, h = z % nh;
+  const int64_t base = (int64_t)b * Sq * 3 * H + h * 64;
+  const __bf16* Qp = qkv + base;
+  const __bf16* Kp = Qp + H;
+  const __bf16* Vp = Qp + 2 * H;
+  const __bf16* dOp = dO + (int64_t)b * Sq * H + h * 64;
+  const float* lsep = lse + (int64_t)z * Sq;
+  const float* Dp = D + (int64_t)z * Sq;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int w = tid >> 6;
+  const int il = lane & 31, kh = lane >> 5;
+  const int q0 = blockIdx.x * 128 + w * 32;
+  const int myq = q0 + il;
+  const float mylse = lsep[myq];
+  const float myD = Dp[myq];
+
+  bf16x8 qf[4], df[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    qf[s] = *reinterpret_cast<const bf16x8*>(
+        Qp + (int64_t)myq * 3 * H + s * 16 + kh * 8);
+    df[s] = *reinterpret_cast<const bf16x8*>(
+        dOp + (int64_t)myq * H + s * 16 + kh * 8);
+  }
+
+  // staging map: 256 threads x 2 rows each (row r and r+32), 16 B chunks
+  const int srow = tid >> 3, schunk = tid & 7;  // rows 0..31
+  const int so0 = nt_off(srow, schunk), so1 = nt_off(srow + 32, schunk);
+  auto stage = [&](int buf, int kv0) {
+    *reinterpret_cast<bf16x8*>(&kbuf[buf][so0]) =
+        *reinterpret_cast<const bf16x8*>(
+            Kp + (int64_t)(kv0 + srow) * 3 * H + schunk * 8);
+    *reinterpret_cast<bf16x8*>(&kbuf[buf][so1]) =
+        *reinterpret_cast<const bf16x8*>(
+            Kp + (int64_t)(kv0 + srow + 32) * 3 * H + schunk * 8);
+    *reinterpret_cast<bf16x8*>(&vbuf[buf][so0]) =
+        *reinterpret_cast<const bf16x8*>(
+            Vp + (int64_t)(kv0 + srow) * 3 * H + schunk * 8);
+    *reinterpret_cast<bf16x8*>(&vbuf[buf][so1]) =
+        *reinterpret_cast<const bf16x8*>(
+            Vp + (int64_t)(kv0 + srow + 32) * 3 * H + schunk * 8);
+  };
+
+  const int ntiles = (blockIdx.x * 128 + 128) / 64;  // block-uniform
+  stage(0, 0);
+  __syncthreads();
+
+  f32x16 dq0 = {}, dq1 = {};
+  for (int kvt = 0; kvt < ntiles; ++kvt) {
+    const int kv0 = kvt * 64;
+    if (kvt + 1 < ntiles) stage((kvt + 1) & 1, kv0 + 64);
+    const bool active = kv0 <= q0 + 31;  // wave-uniform causal skip
+    if (active) {
+      const __bf16* kb = kbuf[kvt & 1];
+      const __bf16* vb = vbuf[kvt & 1];
+      // two kv sub-tiles: independent S and dP chains
+      f32x16 s0 = {}, s1 = {}, p0 = {}, p1 = {};
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int ch = s * 2 + kh;
+        const bf16x8 ka =
+            *reinterpret_cast<const bf16x8*>(&kb[nt_off(il, ch)]);
+        const bf16x8 kb2 =
+            *reinterpret_cast<const bf16x8*>(&kb[nt_off(32 + il, ch)]);
+        const bf16x8 va =
+            *reinterpret_cast<const bf16x8*>(&vb[nt_off(il, ch)]);
+        const bf16x8 vb2 =
+            *reinterpret_cast<const bf16x8*>(&vb[nt_off(32 + il, ch)]);
+        s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qf[s], s0, 0, 0, 0);
+        s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kb2, qf[s], s1, 0, 0,
+                                                     0);
+        p0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, df[s], p0, 0, 0, 0);
+        p1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vb2, df[s], p1, 0, 0,
+                                                     0);
+      }
+      float dsv[32];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int kv = kv0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+        const bool ok0 = kv <= myq;
+        const bool ok1 = kv + 32 <= myq;
+        const float pa = ok0 ? __expf(s0[r] * scale - mylse) : 0.f;
+        const float pb = ok1 ? __expf(s1[r] * scale - mylse) : 0.f;
+        dsv[r] = ok0 ? pa * (p0[r] - myD) : 0.f;
+        dsv[16 + r] = ok1 ? pb * (p1[r] - myD) : 0.f;
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const bf16x8 da = bf_dance(dsv + t * 8);
+        // B[k = kv 16t+8kh..+7][n = d]: columns of the row-major K tile
+        const bf16x8 kt0 = nt_tr_frag(kb, lane, t * 16 + kh * 8, 0);
+        const bf16x8 kt1 = nt_tr_frag(kb, lane, t * 16 + kh * 8, 1);
+        dq0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, kt0, dq0, 0, 0, 0);
+        dq1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, kt1, dq1, 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+  __bf16* dQp = dqkv + base;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int q = q0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+    dQp[(int64_t)q * 3 * H + il] = (__bf16)(scale * dq0[r]);
+    dQp[(int64_t)q * 3 * H + 32 + il] = (__bf16)(scale * dq1[r]);
+  }
+  if (dbias) {  // kernel-uniform
+    float c0 = 0.f, c1 = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      c0 += scale * dq0[r];
+      c1 += scale * dq1[r];
+    }
+    c0 += __shfl_xor(c0, 32, 64);
+    c1 += __shfl_xor(c1, 32, 64);
+    if (kh == 0) {
+      red[w * 64 + il] = c0;
+      red[w * 64 + 32 + il] = c1;
+    }
+    __syncthreads();
+    if (tid < 64)
+      atomicAdd(dbias + h * 64 + tid, (red[tid] + red[64 + tid]) +
+                                          (red[128 + tid] + red[192 + tid]));
+  }
+}
+
+extern "C" int ob_flash_bwd_nt_bf16(const void* qkv, const void* dO,
+                                    const void* lse, const void* D,
+                                    void* dqkv, void* dbias_qkv, int64_t B,
+                                    int64_t Sq, int64_t H, int64_t nh,
+                                    float scale, void* stream) {
+  if (H / nh != 64) return ob_fail("flash_bwd_nt: head_dim must be 64");
+  if (Sq % 128) return ob_fail("flash_bwd_nt: S must be a multiple of 128");
+  dim3 gridp((unsigned)(Sq / 64), 1, (unsigned)(B * nh));
+  k_flash_bwd_dkdv_nt<<<gridp, 256, 0, S(stream)>>>(
+      (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse,
+      (const float*)D, (__bf16*)dqkv, (float*)dbias_qkv, (int)Sq, (int)H,
+      (int)nh, scale);
+  OB_LAUNCH_CHECK();
+  dim3 grid((unsigned)(Sq / 128), 1, (unsigned)(B * nh));
+  k_flash_bwd_dq_nt<<<grid, 256, 0, S(stream)>>>(
+      (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse,
+      (const float*)D, (__bf16*)dqkv, (float*)dbias_qkv, (int)Sq, (int)H,
+      (int)nh, scale);
+  OB_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
 // 256x256 8-phase NT GEMM (the guide's fast template: glds staging,
 // st_16x32 LDS swizzle, per-phase ds_read || glds || MFMA interleave,
 // counted vmcnt once per K-tile, raw barriers, 1 block/CU).

@@ -31,8 +31,8 @@ struct Workspace {
   float* bsh2 = nullptr;   // [B, S, H]
   float* dqkv = nullptr;   // [B, S, 3H]
   float* b4h = nullptr;    // [B, S, 4H]
-  float* t1 = nullptr;     // bf16 [dim, BS] transposed operand (as floats)
-  float* t2 = nullptr;
+  float* t1 = nullptr;     // flash backward: D [B*nh, S]; with OB_FLASH_TR=0
+  float* t2 = nullptr;     // also the bf16 transposed operands (t2: fwd V^T)
   float* s1 = nullptr;     // side-stream dW transpose buffers (bf16 as
   float* s2 = nullptr;     // floats): the dW family runs on g_side
   // dropout only (never allocated without it).  pd_f belongs to the
@@ -242,6 +242,18 @@ static bool flash_eligible(const ob_layer_desc* d, float attn_pdrop = 0.f) {
          d->seq_len % 128 == 0;
 }
 
+// The flash path reads its column-major MFMA operands from the row-major LDS
+// tiles (ob_flash_*_nt_bf16): no V^T / Q^T / K^T / dO^T copies, and the
+// b_qkv bias grad comes from the backward kernels' accumulators.
+// OB_FLASH_TR=0 (read once) keeps the transposes + old kernels + colsum.
+static bool flash_tr() {
+  static const bool on = [] {
+    const char* e = getenv("OB_FLASH_TR");
+    return !(e && e[0] == '0');
+  }();
+  return on;
+}
+
 // parameter offsets (canonical layout, oracle/gpt2_oracle.py::layer_param_spec)
 struct BlockParams {
   int64_t ln1_w, ln1_b, w_qkv, b_qkv, w_attnproj, b_attnproj, ln2_w, ln2_b,
@@ -391,8 +403,13 @@ static int layer_create(const ob_layer_desc* d, const ob_dropout_desc* drop,
     if (ws_ensure(&g_ws.dqkv, &g_ws.sz_dqkv, BS * 3 * H)) return 1;
     if (ws_ensure(&g_ws.b4h, &g_ws.sz_b4h, BS * 4 * H)) return 1;
     if (d->dtype == 1) {
-      if (ws_ensure(&g_ws.t1, &g_ws.sz_t1, (4 * H * BS + 1) / 2)) return 1;
-      if (ws_ensure(&g_ws.t2, &g_ws.sz_t2, (4 * H * BS + 1) / 2)) return 1;
+      if (l->flash && flash_tr()) {
+        // only the flash backward's D = rowsum(dO * O), [Bm*nh, S] floats
+        if (ws_ensure(&g_ws.t1, &g_ws.sz_t1, Bm * nh * Sq)) return 1;
+      } else {
+        if (ws_ensure(&g_ws.t1, &g_ws.sz_t1, (4 * H * BS + 1) / 2)) return 1;
+        if (ws_ensure(&g_ws.t2, &g_ws.sz_t2, (4 * H * BS + 1) / 2)) return 1;
+      }
       if (ws_ensure(&g_ws.s1, &g_ws.sz_s1, (4 * H * BS + 1) / 2)) return 1;
       if (ws_ensure(&g_ws.s2, &g_ws.sz_s2, (4 * H * BS + 1) / 2)) return 1;
       if (side_init()) return 1;
@@ -760,10 +777,17 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
                       p + bp.b_qkv, nullptr, 0, 1, stream)))
     return 1;
   __bf16* am = (__bf16*)(st + l->o_attnm);
-  if (use_flash(l)) {
-    // V^T materialization (workspace, transient within this call), then
+  if (use_flash(l) && flash_tr()) {
     // the fused kernel writes O and the per-row LSE (stored where the
-    // materialized-P path keeps P).
+    // materialized-P path keeps P)
+    float* lseP = st + l->o_p;
+    if (OB_PROF(OB_PF_FLASH_FWD, stream,
+                ob_flash_fwd_nt_bf16(qkv, am, lseP, B, Sq, H, nh,
+                                     1.f / sqrtf((float)hd), stream)))
+      return 1;
+  } else if (use_flash(l)) {
+    // OB_FLASH_TR=0: V^T materialization (workspace, transient within this
+    // call) feeding the kernel that takes a transposed V
     __bf16* VTw = (__bf16*)g_ws.t2;
     if (OB_PROF(OB_PF_FLASH_FWD, stream,
                 ob_transpose_bf16_b(qkv + 2 * H, VTw, Sq, 64, Sq * 3 * H, 64,
@@ -990,7 +1014,20 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   hipEvent_t ev_din_done = side_evt();
   OB_HIP(hipEventRecord(ev_din_done, g_side.stream));
   // ---- attention core ----
-  if (use_flash(l)) {
+  const bool flash_nt = use_flash(l) && flash_tr();
+  if (flash_nt) {
+    float* Dbuf = g_ws.t1;
+    const float* lseP = st + l->o_p;
+    if (OB_PROF(OB_PF_FLASH_BWD, stream,
+                ob_flash_dsum_bf16(am, DATT, Dbuf, B, Sq, H, nh, stream)))
+      return 1;
+    // also adds the b_qkv grad (column sums of DQKV) from its accumulators
+    if (OB_PROF(OB_PF_FLASH_BWD, stream,
+                ob_flash_bwd_nt_bf16(qkv, DATT, lseP, Dbuf, DQKV,
+                                     g + bp.b_qkv, B, Sq, H, nh, scale,
+                                     stream)))
+      return 1;
+  } else if (use_flash(l)) {
     const int64_t BSH = BS * H;
     __bf16* QTw = (__bf16*)g_ws.t1;
     __bf16* KTw = QTw + BSH;
@@ -1060,7 +1097,8 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   }
   // ---- QKV projection ----
   OB_SIDE_FENCE(S(stream), g_side.stream);  // DQKV ready
-  if (OB_PROF(OB_PF_ELEM, side,
+  if (!flash_nt &&
+      OB_PROF(OB_PF_ELEM, side,
               ob_colsum_bf16(DQKV, g + bp.b_qkv, BS, 3 * H, side)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DW, side,

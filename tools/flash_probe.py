@@ -94,3 +94,67 @@ for dkdv, dq, name in [("s", "", "split+v3"), ("3", "", "v3+v3   "),
     print(f"flash_bwd {name} {ms*1e3:8.1f} us  {fl_bwd/ms/1e9:6.0f} TF "
           f"(dkdv+dq together)")
 print(f"speedup v3 vs round1: {results['round1  ']/results['v3+v3   ']:.3f}x")
+
+# ---- transposed copies + old kernels vs the no-transpose entry points ----
+# (what ob_layer.hip runs per block-microbatch under OB_FLASH_TR=0 / =1).
+# Per-kernel times: run this file under a kernel trace (tools/kstats.py).
+os.environ.pop("OB_FLASH_PAIR", None)
+os.environ.pop("OB_FLASH_DQ", None)
+V_ptr = ctypes.c_void_p(qkv.data_ptr() + 2 * H * 2)
+K_ptr = ctypes.c_void_p(qkv.data_ptr() + H * 2)
+dbias = torch.zeros(3 * H, device=DEV)
+
+
+def tr(src, dst, sb, ld):
+    check(ext.ob_transpose_bf16_b(src, ptr(dst), S, hd, sb, hd, ld, B, nh,
+                                  stream()))
+
+
+def fwd_old():
+    tr(V_ptr, VT, S * 3 * H, 3 * H)
+    check(ext.ob_flash_fwd_bf16(ptr(qkv), ptr(VT), ptr(O), ptr(lse), B, S, H,
+                                nh, scale, stream()))
+
+
+def fwd_new():
+    check(ext.ob_flash_fwd_nt_bf16(ptr(qkv), ptr(O), ptr(lse), B, S, H, nh,
+                                   scale, stream()))
+
+
+def bwd_old(colsum=False):
+    tr(ptr(qkv), QT, S * 3 * H, 3 * H)
+    tr(K_ptr, KT, S * 3 * H, 3 * H)
+    tr(ptr(dO), dOT, S * H, H)
+    check(ext.ob_flash_bwd_bf16(
+        ptr(qkv), ptr(QT), ptr(KT), ptr(dOT), ptr(dO), ptr(lse), ptr(D),
+        ptr(dqkv), B, S, H, nh, scale, stream()))
+    if colsum:
+        check(ext.ob_colsum_bf16(ptr(dqkv), ptr(dbias), B * S, 3 * H,
+                                 stream()))
+
+
+def bwd_new(bias=None):
+    check(ext.ob_flash_bwd_nt_bf16(
+        ptr(qkv), ptr(dO), ptr(lse), ptr(D), ptr(dqkv), ptr(bias), B, S, H,
+        nh, scale, stream()))
+
+
+O_old = torch.empty_like(O)
+fwd_old()
+O_old.copy_(O)
+fwd_new()
+dq_old = torch.empty_like(dqkv)
+bwd_old()
+dq_old.copy_(dqkv)
+bwd_new()
+torch.cuda.synchronize()
+print(f"nt outputs bit-identical: fwd {torch.equal(O, O_old)} "
+      f"bwd {torch.equal(dqkv, dq_old)}")
+rows = [("fwd  transpose + v4          ", fwd_old),
+        ("fwd  nt                      ", fwd_new),
+        ("bwd  3 transposes + dkdv + dq", bwd_old),
+        ("bwd  nt (dkdv + dq)          ", bwd_new),
+        ("bwd  old + colsum(dqkv)      ", lambda: bwd_old(True)),
+        ("bwd  nt + bias in-kernel     ", lambda: bwd_new(dbias))]
+for name, fn in rows:
+    print(f"{name} {timeit(fn)*1e3:8.1f} us")
