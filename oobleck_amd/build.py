@@ -9,6 +9,7 @@ PKG_DIR = pathlib.Path(__file__).resolve().parent
 SO_PATH = PKG_DIR / "libob_stage.so"
 SOURCES = [PKG_DIR / "csrc" / "ob_kernels.hip",
            PKG_DIR / "csrc" / "ob_kernels_bf16.hip",
+           PKG_DIR / "csrc" / "ob_flash_bf16.hip",
            PKG_DIR / "csrc" / "ob_blaslt.hip",
            PKG_DIR / "csrc" / "ob_optim.hip",
            PKG_DIR / "csrc" / "ob_dropout.hip",

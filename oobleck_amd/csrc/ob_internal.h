@@ -112,7 +112,8 @@ int ob_embed_bwd_drop(const ob_drop_key& key, int bf16, const int64_t* ids,
                       const void* dout, float* dwte, float* dwpe, int64_t B,
                       int64_t Sq, int64_t H, void* stream);
 
-// bf16-path launchers (defined in ob_kernels_bf16.hip)
+// bf16-path launchers (defined in ob_kernels_bf16.hip; the flash family
+// and ob_transpose_bf16_b in ob_flash_bf16.hip)
 extern "C" {
 int ob_f32_to_bf16_t_ld(const void* x, void* y, int64_t rows, int64_t cols,
                         int64_t out_ld, void* stream);

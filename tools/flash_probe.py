@@ -1,8 +1,10 @@
-# Within-box A/B of the flash backward kernels at the step shape
-# (B=8, nh=12, S=1024, head_dim 64): round-1 2-occupancy dkdv vs the
-# paired-wave 3/4-occupancy dkdv (OB_FLASH_PAIR), plus dq and fwd.
+# Within-box A/B of the two flash-attention paths at the step shape
+# (B=8, nh=12, S=1024, head_dim 64): transposed copies + the
+# transposed-operand kernels (what ob_layer.hip runs per block-microbatch
+# under OB_FLASH_TR=0) vs the production `_nt` entry points.  Prints whether
+# the outputs are bit-identical, then one timing row per path.
+# Per-kernel times: run this file under a kernel trace (tools/kstats.py).
 import ctypes
-import os
 import pathlib
 import sys
 
@@ -54,52 +56,6 @@ KT = torch.empty_like(VT)
 dOT = torch.empty_like(VT)
 scale = ctypes.c_float(1.0 / hd ** 0.5)
 
-check(ext.ob_transpose_bf16_b(ptr(qkv) if False else
-                              ctypes.c_void_p(qkv.data_ptr() + 2 * H * 2),
-                              ptr(VT), S, hd, S * 3 * H, hd, 3 * H, B, nh,
-                              stream()))
-# causal attention fwd flops: 2 matmuls, ~half masked
-fl_fwd = 2 * 2 * B * nh * S * S * hd / 2
-for mode, name in [("4", "v4-4wave "), ("3", "v3-ladder"),
-                   ("pf", "pipelined"), ("v1", "round1   ")]:
-    os.environ["OB_FLASH_FWD"] = mode
-    ms = timeit(lambda: check(ext.ob_flash_fwd_bf16(
-        ptr(qkv), ptr(VT), ptr(O), ptr(lse), B, S, H, nh, scale, stream())))
-    print(f"flash_fwd {name} {ms*1e3:8.1f} us  {fl_fwd/ms/1e9:6.0f} TF")
-os.environ.pop("OB_FLASH_FWD", None)
-
-check(ext.ob_transpose_bf16_b(ptr(qkv), ptr(QT), S, hd, S * 3 * H, hd,
-                              3 * H, B, nh, stream()))
-check(ext.ob_transpose_bf16_b(ctypes.c_void_p(qkv.data_ptr() + H * 2),
-                              ptr(KT), S, hd, S * 3 * H, hd, 3 * H, B, nh,
-                              stream()))
-check(ext.ob_transpose_bf16_b(ptr(dO), ptr(dOT), S, hd, S * H, hd, H, B,
-                              nh, stream()))
-check(ext.ob_flash_dsum_bf16(ptr(O), ptr(dO), ptr(D), B, S, H, nh, stream()))
-
-fl_bwd = 4 * 2 * B * nh * S * S * hd / 2 + 3 * 2 * B * nh * S * S * hd / 2
-results = {}
-for dkdv, dq, name in [("s", "", "split+v3"), ("3", "", "v3+v3   "),
-                       ("p", "", "pair+v3 "), ("p", "1", "pair+pf "),
-                       ("0", "1", "round1  ")]:
-    os.environ["OB_FLASH_PAIR"] = dkdv
-    if dq:
-        os.environ["OB_FLASH_DQ"] = dq
-    else:
-        os.environ.pop("OB_FLASH_DQ", None)
-    ms = timeit(lambda: check(ext.ob_flash_bwd_bf16(
-        ptr(qkv), ptr(QT), ptr(KT), ptr(dOT), ptr(dO), ptr(lse), ptr(D),
-        ptr(dqkv), B, S, H, nh, scale, stream())))
-    results[name] = ms
-    print(f"flash_bwd {name} {ms*1e3:8.1f} us  {fl_bwd/ms/1e9:6.0f} TF "
-          f"(dkdv+dq together)")
-print(f"speedup v3 vs round1: {results['round1  ']/results['v3+v3   ']:.3f}x")
-
-# ---- transposed copies + old kernels vs the no-transpose entry points ----
-# (what ob_layer.hip runs per block-microbatch under OB_FLASH_TR=0 / =1).
-# Per-kernel times: run this file under a kernel trace (tools/kstats.py).
-os.environ.pop("OB_FLASH_PAIR", None)
-os.environ.pop("OB_FLASH_DQ", None)
 V_ptr = ctypes.c_void_p(qkv.data_ptr() + 2 * H * 2)
 K_ptr = ctypes.c_void_p(qkv.data_ptr() + H * 2)
 dbias = torch.zeros(3 * H, device=DEV)
@@ -143,6 +99,7 @@ O_old = torch.empty_like(O)
 fwd_old()
 O_old.copy_(O)
 fwd_new()
+check(ext.ob_flash_dsum_bf16(ptr(O), ptr(dO), ptr(D), B, S, H, nh, stream()))
 dq_old = torch.empty_like(dqkv)
 bwd_old()
 dq_old.copy_(dqkv)
