@@ -313,6 +313,26 @@ int ob_flash_bwd_nt_bf16(const void* qkv, const void* dO, const void* lse,
                          const void* D, void* dqkv, void* dbias_qkv,
                          int64_t B, int64_t Sq, int64_t H, int64_t nh,
                          float scale, void* stream);
+/* The same backward without a D input: the dq kernel forms D from O and dO
+ * (bit-identical to ob_flash_dsum_bf16's), writes it to D_ws (fp32
+ * [B*nh, Sq]) and the dkdv kernel, launched after it, reads it there. */
+int ob_flash_bwd_nt_d_bf16(const void* qkv, const void* O, const void* dO,
+                           const void* lse, void* D_ws, void* dqkv,
+                           void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
+                           int64_t nh, float scale, void* stream);
+/* Host-only queries of the block -> work mapping of the three kernels above
+ * (no GPU call).  kind: 0 forward, 1 dq, 2 dkdv.
+ * rows: unit = wave 0..3 (forward, dq) or wave pair 0..1 (dkdv) of `block`
+ *   -> the first of its 32 rows and the tile range it computes; unit = -1 ->
+ *   the tile range the block stages (row0 = -1).  Tiles: 64 kv rows for
+ *   forward and dq, 32 q rows for dkdv.
+ * grid: blocks launched for Z = B*nh heads, padding included.
+ * id: linear block id -> (z, block); returns 1, or 0 for a padding id. */
+int ob_flash_fold_rows(int64_t kind, int64_t Sq, int64_t block, int64_t unit,
+                       int64_t* row0, int64_t* first_tile, int64_t* n_tiles);
+int64_t ob_flash_fold_grid(int64_t kind, int64_t Sq, int64_t Z);
+int ob_flash_fold_id(int64_t kind, int64_t Sq, int64_t Z, int64_t id,
+                     int64_t* z, int64_t* block);
 
 /* dtype casts (weight shadows / activation conversion). */
 int ob_f32_to_bf16(const void* x, void* y, int64_t n, void* stream);

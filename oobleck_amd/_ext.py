@@ -149,6 +149,13 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
                                          f32, vp]
     lib.ob_flash_bwd_nt_bf16.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64,
                                          i64, i64, f32, vp]
+    lib.ob_flash_bwd_nt_d_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64,
+                                           i64, i64, i64, f32, vp]
+    p64 = ctypes.POINTER(ctypes.c_int64)
+    lib.ob_flash_fold_rows.argtypes = [i64, i64, i64, i64, p64, p64, p64]
+    lib.ob_flash_fold_grid.argtypes = [i64, i64, i64]
+    lib.ob_flash_fold_grid.restype = ctypes.c_int64
+    lib.ob_flash_fold_id.argtypes = [i64, i64, i64, i64, p64, p64]
     return lib
 
 

@@ -3,7 +3,8 @@
 //
 // Two families of the same three kernels (forward, dK/dV, dQ):
 //   1. production: k_flash_fwd_nt / k_flash_bwd_dkdv_nt / k_flash_bwd_dq_nt
-//      (ob_flash_fwd_nt_bf16, ob_flash_bwd_nt_bf16), plus k_flash_dsum;
+//      (ob_flash_fwd_nt_bf16, ob_flash_bwd_nt_bf16 and, with D formed in
+//      the dq kernel, ob_flash_bwd_nt_d_bf16), plus k_flash_dsum;
 //   2. their transposed-operand twins k_flash_fwd_bf16_v4 /
 //      k_flash_bwd_dkdv_s / k_flash_bwd_dq_v3 (ob_flash_fwd_bf16,
 //      ob_flash_bwd_bf16) fed by k_transpose_bf16_b — the reference of the
@@ -17,8 +18,17 @@
 //   B: lane holds B[k = 8*kh + j][n = il]
 //   C/D: col = il, row = acc_row(r, kh) = (r&3) + 8*(r>>2) + 4*kh
 //
-// Forward: per (b, h, 128-row q-tile) block of 4 waves; each wave owns 32
-// q rows.  QK^T is computed SWAPPED (mfma(A=K, B=Q)) so each lane holds the
+// Which rows a production block owns and which linear block id is which
+// (head, block) is ob_flash_fold.h: a block takes a
+// light and a heavy piece of the causal triangle so all blocks of a launch
+// cost the same, and the blocks of one head get ids of one XCD so they share
+// its L2.  The twins keep the plain map (blockIdx.x = tile, blockIdx.z =
+// head); a wave's arithmetic does not depend on the map, so the two
+// families stay bit-identical (tests/test_gpu_flash_fold.py).
+//
+// Forward: per (b, h) blocks of 4 waves, each wave owns 32 q rows (twins:
+// one 128-row q-tile; production: two 64-row halves, ob_flash_fold.h).
+// QK^T is computed SWAPPED (mfma(A=K, B=Q)) so each lane holds the
 // scores of ONE q column (q = il, 16 kv rows per accumulator) — the
 // online-softmax row reduce is lane-local + one shfl_xor(32) partner
 // combine.  P converts to the PV A-fragment with 8 pack-to-bf16 ops + 2
@@ -28,7 +38,8 @@
 // Writes O (bf16) and the per-row LSE (fp32) for the backward recompute.
 //
 // Backward (recompute from Q, K, LSE; no stored P):
-//   D[z][q]   = sum_d dO[q,d] * O[q,d]                    (k_flash_dsum)
+//   D[z][q]   = sum_d dO[q,d] * O[q,d]     (k_flash_dsum; in production
+//               the dq kernel forms it: ob_flash_bwd_nt_d_bf16)
 //   dKdV      : blocks own 64 kv rows, loop q-tiles:
 //               S = QK^T (acc col = kv), P = exp(scale*S - lse[q]),
 //               dP = dO V^T-free (mfma(dO, V)), dS = P*(dP - D[q]),
@@ -49,6 +60,7 @@
 // 4 waves because the per-tile barrier makes a block wait for its longest
 // causal diagonal.
 #include "ob_internal.h"
+#include "ob_flash_fold.h"
 
 #include <cmath>
 
@@ -181,17 +193,22 @@ __device__ __forceinline__ bf16x8 nt_tr_frag(const __bf16* tile, int lane,
 //   * 128 q-rows per block, not 256: the per-tile barrier makes every wave
 //     wait for the block's longest causal diagonal, and 4 waves halve that
 //     spread (57 vs 71.5 us at the step shape).
+//   * the 128 rows are the 64-row halves a and n64-1-a (ob_flash_fold.h):
+//     waves 0,1 go inactive after the light half's diagonal and only stage
+//     and barrier from there on.
 //   * the O rescale is skipped while no row's max grows by more than 8;
 //     tiles wholly below the diagonal skip the causal mask.
 // vbuf is staged from V rows like kbuf from K rows; the PV B fragments are
 // its columns.
 __global__ __launch_bounds__(256, 3) void k_flash_fwd_nt(
     const __bf16* __restrict__ qkv, __bf16* __restrict__ Obase,
-    float* __restrict__ lse, int Sq, int H, int nh, float scale) {
+    float* __restrict__ lse, int Sq, int H, int nh, int Z, float scale) {
   __shared__ __attribute__((aligned(16))) __bf16 kbuf[2][64 * 64];
   __shared__ __attribute__((aligned(16))) __bf16 vbuf[2][64 * 64];
   __shared__ float bcast[128];
-  const int z = blockIdx.z;
+  int blk, z;
+  if (!ob_fold_id(blockIdx.x, ob_fold_q_nblk(Sq), Z, &blk, &z))
+    return;  // block-uniform: grid padding
   const int b = z / nh, h = z % nh;
   const int64_t qoff = (int64_t)b * Sq * 3 * H + h * 64;
   const __bf16* Qp = qkv + qoff;
@@ -204,9 +221,9 @@ __global__ __launch_bounds__(256, 3) void k_flash_fwd_nt(
   const int lane = tid & 63;
   const int w = tid >> 6;
   const int il = lane & 31, kh = lane >> 5;
-  const int q0b = blockIdx.x * 128;
-  const int q0 = q0b + w * 32;
+  const int q0 = ob_fold_q_row0(Sq, blk, w);
   const int myq = q0 + il;
+  const int mytiles = ob_fold_q_wave_tiles(q0);
 
   // staging: thread covers chunks tid and tid+256 of the 512-slot tile
   const int sr0 = tid >> 3, sr1 = sr0 + 32, sc = tid & 7;
@@ -232,7 +249,7 @@ __global__ __launch_bounds__(256, 3) void k_flash_fwd_nt(
     qf[s] = *reinterpret_cast<const bf16x8*>(
         Qp + (int64_t)myq * 3 * H + s * 16 + kh * 8);
 
-  const int ntiles = (q0b + 128) / 64;
+  const int ntiles = ob_fold_q_block_tiles(Sq, blk);  // block-uniform
   stage(0, 0);
   __syncthreads();
 
@@ -241,7 +258,7 @@ __global__ __launch_bounds__(256, 3) void k_flash_fwd_nt(
   for (int kvt = 0; kvt < ntiles; ++kvt) {
     const int kv0 = kvt * 64;
     if (kvt + 1 < ntiles) stage((kvt + 1) & 1, kv0 + 64);
-    const bool active = kv0 <= q0 + 31;
+    const bool active = kvt < mytiles;  // kv0 <= q0 + 31, wave-uniform
     if (active) {
       const __bf16* kb = kbuf[kvt & 1];
       const __bf16* vb = vbuf[kvt & 1];
@@ -336,16 +353,16 @@ extern "C" int ob_flash_fwd_nt_bf16(const void* qkv, void* O, void* lse,
                                     int64_t nh, float scale, void* stream) {
   if (H / nh != 64) return ob_fail("flash_fwd_nt: head_dim must be 64");
   if (Sq % 128) return ob_fail("flash_fwd_nt: S must be a multiple of 128");
-  dim3 grid((unsigned)(Sq / 128), 1, (unsigned)(B * nh));
-  k_flash_fwd_nt<<<grid, 256, 0, S(stream)>>>(
-      (const __bf16*)qkv, (__bf16*)O, (float*)lse, (int)Sq, (int)H, (int)nh,
-      scale);
+  const int Z = (int)(B * nh);
+  k_flash_fwd_nt<<<ob_fold_grid(ob_fold_q_nblk((int)Sq), Z), 256, 0,
+                   S(stream)>>>((const __bf16*)qkv, (__bf16*)O, (float*)lse,
+                                (int)Sq, (int)H, (int)nh, Z, scale);
   OB_LAUNCH_CHECK();
   return 0;
 }
 
 // dK/dV: split-duty wave pairs.  A block owns 64 kv rows, a WAVE PAIR one
-// 32-kv-row tile; both loop over the q-tiles from the diagonal down.
+// 32-kv-row tile; each loops over the q-tiles from its diagonal down.
 //   role 0: K resident, owns the whole P chain: S -> P -> BOTH d-halves of dV
 //   role 1: V resident, owns the whole dS chain: dP -> dS -> BOTH d-halves
 //           of dK
@@ -357,8 +374,10 @@ extern "C" int ob_flash_fwd_nt_bf16(const void* qkv, void* O, void* lse,
 // the exp + causal mask entirely (masked P is already 0), and each wave
 // runs HALF the lse/D shuffle fan-out: 208.6 us whole-backward vs 231.2
 // for pairs that exchange both S and dP (profiles/r02_flash_probe.log).
-// The causal q-loop start is block-uniform; the sub-diagonal tile pair 1
-// wastes is masked per element (p = 0).
+// The block's pairs own the kv tiles x and n32-1-x (ob_flash_fold.h); the
+// q loop starts at pair 0's diagonal and pair 1 idles, staging and
+// meeting the barrier only, until the loop reaches its own.  (The twin's
+// pair 1 instead spends one masked, all-zero tile above its diagonal.)
 // Q and dO tiles (the A fragments, read before the exchange barrier) are
 // staged in LDS once per block, double-buffered under that ONE barrier per
 // q-tile.  The dV/dK B operands (dO^T for role 0, Q^T for role 1) are
@@ -371,12 +390,14 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dkdv_nt(
     const __bf16* __restrict__ qkv, const __bf16* __restrict__ dO,
     const float* __restrict__ lse, const float* __restrict__ D,
     __bf16* __restrict__ dqkv, float* __restrict__ dbias, int Sq, int H,
-    int nh, float scale) {
+    int nh, int Z, float scale) {
   __shared__ float xch[2][2][32 * 32];  // [buffer][pair][P tile]
   __shared__ __attribute__((aligned(16))) __bf16 qbuf[2][32 * 64];
   __shared__ __attribute__((aligned(16))) __bf16 obuf[2][32 * 64];
   __shared__ float red[4 * 64];
-  const int z = blockIdx.z;
+  int blk, z;
+  if (!ob_fold_id(blockIdx.x, ob_fold_kv_nblk(Sq), Z, &blk, &z))
+    return;  // block-uniform: grid padding
   const int b = z / nh, h = z % nh;
   const int64_t base = (int64_t)b * Sq * 3 * H + h * 64;
   const __bf16* Qp = qkv + base;
@@ -391,8 +412,9 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dkdv_nt(
   const int w = tid >> 6;
   const int pair = w >> 1, role = w & 1;
   const int il = lane & 31, kh = lane >> 5;
-  const int kv0 = blockIdx.x * 64 + pair * 32;
+  const int kv0 = ob_fold_kv_row0(Sq, blk, pair);
   const int mykv = kv0 + il;
+  const int myqt0 = ob_fold_kv_pair_first(kv0);
 
   const __bf16* KV = role ? Vp : Kp;
   bf16x8 of[4];
@@ -414,13 +436,20 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dkdv_nt(
 
   f32x16 acc0 = {}, acc1 = {};  // role 0: dV d-halves; role 1: dK d-halves
   const int nqt = Sq / 32;
-  const int qt0 = (blockIdx.x * 64) / 32;
+  const int qt0 = ob_fold_kv_block_first(blk);  // block-uniform
   stage(qt0 & 1, qt0 * 32);
   __syncthreads();
 
   for (int qt = qt0; qt < nqt; ++qt) {
     const int q0 = qt * 32;
     if (qt + 1 < nqt) stage((qt + 1) & 1, q0 + 32);
+    // wave-uniform: pair 1 idles (staging and the barrier only) until the
+    // loop reaches its diagonal, q0 + 31 >= kv0.  Each wave meets exactly
+    // one barrier per iteration on either side of the branch.
+    if (qt < myqt0) {
+      __syncthreads();
+      continue;
+    }
     // own tile's A image, and the B image: role 0 multiplies P^T by dO,
     // role 1 dS^T by Q
     const __bf16* ab = role ? obuf[qt & 1] : qbuf[qt & 1];
@@ -516,15 +545,27 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dkdv_nt(
 // Bound 3 (not the twin's 2): the twin compiles to 167 VGPRs and so
 // already runs 3 waves/SIMD; this body came to 169 under bound 2, which
 // would have dropped it to 2.
+// kFormD: D is not an input.  Each wave forms D[q] = sum_d dO[q,d] * O[q,d]
+// of its 32 rows from the dO fragments it holds anyway and O loaded in the
+// same layout, uses it, and writes it to Dout for the dkdv launch that
+// follows.  A lane holds the 8-element chunks 2s + kh of its row; the sum
+// is taken in k_flash_dsum's order (chunk sums left to right, then
+// ((c0+c4)+(c2+c6)) + ((c1+c5)+(c3+c7))), so D is bit-identical to that
+// kernel's: the bf16 x bf16 products are exact in fp32, so contraction to
+// fma cannot move a bit either.
+template <bool kFormD>
 __global__ __launch_bounds__(256, 3) void k_flash_bwd_dq_nt(
     const __bf16* __restrict__ qkv, const __bf16* __restrict__ dO,
     const float* __restrict__ lse, const float* __restrict__ D,
+    const __bf16* __restrict__ O, float* __restrict__ Dout,
     __bf16* __restrict__ dqkv, float* __restrict__ dbias, int Sq, int H,
-    int nh, float scale) {
+    int nh, int Z, float scale) {
   __shared__ __attribute__((aligned(16))) __bf16 kbuf[2][64 * 64];
   __shared__ __attribute__((aligned(16))) __bf16 vbuf[2][64 * 64];
   __shared__ float red[4 * 64];
-  const int z = blockIdx.z;
+  int blk, z;
+  if (!ob_fold_id(blockIdx.x, ob_fold_q_nblk(Sq), Z, &blk, &z))
+    return;  // block-uniform: grid padding
   const int b = z / nh, h = z % nh;
   const int64_t base = (int64_t)b * Sq * 3 * H + h * 64;
   const __bf16* Qp = qkv + base;
@@ -532,16 +573,15 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dq_nt(
   const __bf16* Vp = Qp + 2 * H;
   const __bf16* dOp = dO + (int64_t)b * Sq * H + h * 64;
   const float* lsep = lse + (int64_t)z * Sq;
-  const float* Dp = D + (int64_t)z * Sq;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = tid >> 6;
   const int il = lane & 31, kh = lane >> 5;
-  const int q0 = blockIdx.x * 128 + w * 32;
+  const int q0 = ob_fold_q_row0(Sq, blk, w);
   const int myq = q0 + il;
+  const int mytiles = ob_fold_q_wave_tiles(q0);
   const float mylse = lsep[myq];
-  const float myD = Dp[myq];
 
   bf16x8 qf[4], df[4];
 #pragma unroll
@@ -550,6 +590,26 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dq_nt(
         Qp + (int64_t)myq * 3 * H + s * 16 + kh * 8);
     df[s] = *reinterpret_cast<const bf16x8*>(
         dOp + (int64_t)myq * H + s * 16 + kh * 8);
+  }
+  float myD;
+  if constexpr (kFormD) {
+    const __bf16* Orow = O + (int64_t)b * Sq * H + h * 64 + (int64_t)myq * H;
+    float cs[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const bf16x8 ov =
+          *reinterpret_cast<const bf16x8*>(Orow + s * 16 + kh * 8);
+      float c = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) c += bf2f(ov[j]) * bf2f(df[s][j]);
+      cs[s] = c;
+    }
+    // cs[s] = chunk 2s + kh: this half's bracket, then the other half's
+    const float part = (cs[0] + cs[2]) + (cs[1] + cs[3]);
+    myD = part + __shfl_xor(part, 32, 64);
+    if (kh == 0) Dout[(int64_t)z * Sq + myq] = myD;
+  } else {
+    myD = D[(int64_t)z * Sq + myq];
   }
 
   // staging map: 256 threads x 2 rows each (row r and r+32), 16 B chunks
@@ -570,7 +630,7 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dq_nt(
             Vp + (int64_t)(kv0 + srow + 32) * 3 * H + schunk * 8);
   };
 
-  const int ntiles = (blockIdx.x * 128 + 128) / 64;  // block-uniform
+  const int ntiles = ob_fold_q_block_tiles(Sq, blk);  // block-uniform
   stage(0, 0);
   __syncthreads();
 
@@ -578,7 +638,8 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dq_nt(
   for (int kvt = 0; kvt < ntiles; ++kvt) {
     const int kv0 = kvt * 64;
     if (kvt + 1 < ntiles) stage((kvt + 1) & 1, kv0 + 64);
-    const bool active = kv0 <= q0 + 31;  // wave-uniform causal skip
+    // wave-uniform causal skip: kv0 <= q0 + 31
+    const bool active = kvt < mytiles;
     if (active) {
       const __bf16* kb = kbuf[kvt & 1];
       const __bf16* vb = vbuf[kvt & 1];
@@ -652,6 +713,20 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dq_nt(
   }
 }
 
+static int launch_dkdv_nt(const void* qkv, const void* dO, const void* lse,
+                          const void* D, void* dqkv, void* dbias_qkv,
+                          int64_t B, int64_t Sq, int64_t H, int64_t nh,
+                          float scale, void* stream) {
+  const int Z = (int)(B * nh);
+  k_flash_bwd_dkdv_nt<<<ob_fold_grid(ob_fold_kv_nblk((int)Sq), Z), 256, 0,
+                        S(stream)>>>(
+      (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse,
+      (const float*)D, (__bf16*)dqkv, (float*)dbias_qkv, (int)Sq, (int)H,
+      (int)nh, Z, scale);
+  OB_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int ob_flash_bwd_nt_bf16(const void* qkv, const void* dO,
                                     const void* lse, const void* D,
                                     void* dqkv, void* dbias_qkv, int64_t B,
@@ -659,19 +734,99 @@ extern "C" int ob_flash_bwd_nt_bf16(const void* qkv, const void* dO,
                                     float scale, void* stream) {
   if (H / nh != 64) return ob_fail("flash_bwd_nt: head_dim must be 64");
   if (Sq % 128) return ob_fail("flash_bwd_nt: S must be a multiple of 128");
-  dim3 gridp((unsigned)(Sq / 64), 1, (unsigned)(B * nh));
-  k_flash_bwd_dkdv_nt<<<gridp, 256, 0, S(stream)>>>(
-      (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse,
-      (const float*)D, (__bf16*)dqkv, (float*)dbias_qkv, (int)Sq, (int)H,
-      (int)nh, scale);
-  OB_LAUNCH_CHECK();
-  dim3 grid((unsigned)(Sq / 128), 1, (unsigned)(B * nh));
-  k_flash_bwd_dq_nt<<<grid, 256, 0, S(stream)>>>(
-      (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse,
-      (const float*)D, (__bf16*)dqkv, (float*)dbias_qkv, (int)Sq, (int)H,
-      (int)nh, scale);
+  if (launch_dkdv_nt(qkv, dO, lse, D, dqkv, dbias_qkv, B, Sq, H, nh, scale,
+                     stream))
+    return 1;
+  const int Z = (int)(B * nh);
+  k_flash_bwd_dq_nt<false>
+      <<<ob_fold_grid(ob_fold_q_nblk((int)Sq), Z), 256, 0, S(stream)>>>(
+          (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse,
+          (const float*)D, nullptr, nullptr, (__bf16*)dqkv,
+          (float*)dbias_qkv, (int)Sq, (int)H, (int)nh, Z, scale);
   OB_LAUNCH_CHECK();
   return 0;
+}
+
+// The backward without a separate D pass: dq first (forms D from O and dO,
+// writes it to D_ws), then dkdv, which reads D_ws.
+extern "C" int ob_flash_bwd_nt_d_bf16(const void* qkv, const void* O,
+                                      const void* dO, const void* lse,
+                                      void* D_ws, void* dqkv,
+                                      void* dbias_qkv, int64_t B, int64_t Sq,
+                                      int64_t H, int64_t nh, float scale,
+                                      void* stream) {
+  if (H / nh != 64) return ob_fail("flash_bwd_nt_d: head_dim must be 64");
+  if (Sq % 128) return ob_fail("flash_bwd_nt_d: S must be a multiple of 128");
+  const int Z = (int)(B * nh);
+  k_flash_bwd_dq_nt<true>
+      <<<ob_fold_grid(ob_fold_q_nblk((int)Sq), Z), 256, 0, S(stream)>>>(
+          (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse, nullptr,
+          (const __bf16*)O, (float*)D_ws, (__bf16*)dqkv, (float*)dbias_qkv,
+          (int)Sq, (int)H, (int)nh, Z, scale);
+  OB_LAUNCH_CHECK();
+  return launch_dkdv_nt(qkv, dO, lse, D_ws, dqkv, dbias_qkv, B, Sq, H, nh,
+                        scale, stream);
+}
+
+// Host-only queries of the ob_flash_fold.h mapping (no GPU call), for the
+// tests.  kind: 0 forward, 1 dq, 2 dkdv.
+// ob_flash_fold_rows: unit = wave (0..3; forward, dq) or wave pair (0..1;
+// dkdv) -> its first row (it owns 32) and the tiles it computes; unit = -1
+// -> the tiles the block stages (row0 = -1).  Tiles are 64-row kv tiles for
+// forward and dq, 32-row q tiles for dkdv.
+extern "C" int ob_flash_fold_rows(int64_t kind, int64_t Sq, int64_t block,
+                                  int64_t unit, int64_t* row0,
+                                  int64_t* first_tile, int64_t* n_tiles) {
+  if (Sq <= 0 || Sq % 128) return ob_fail("fold_rows: S must be a multiple of 128");
+  const int S_ = (int)Sq, blk = (int)block;
+  if (kind == OB_FOLD_FWD || kind == OB_FOLD_DQ) {
+    if (blk < 0 || blk >= ob_fold_q_nblk(S_) || unit < -1 || unit > 3)
+      return ob_fail("fold_rows: block/unit out of range");
+    *first_tile = 0;
+    if (unit < 0) {
+      *row0 = -1;
+      *n_tiles = ob_fold_q_block_tiles(S_, blk);
+    } else {
+      *row0 = ob_fold_q_row0(S_, blk, (int)unit);
+      *n_tiles = ob_fold_q_wave_tiles((int)*row0);
+    }
+    return 0;
+  }
+  if (kind == OB_FOLD_DKDV) {
+    if (blk < 0 || blk >= ob_fold_kv_nblk(S_) || unit < -1 || unit > 1)
+      return ob_fail("fold_rows: block/unit out of range");
+    if (unit < 0) {
+      *row0 = -1;
+      *first_tile = ob_fold_kv_block_first(blk);
+    } else {
+      *row0 = ob_fold_kv_row0(S_, blk, (int)unit);
+      *first_tile = ob_fold_kv_pair_first((int)*row0);
+    }
+    *n_tiles = S_ / 32 - *first_tile;
+    return 0;
+  }
+  return ob_fail("fold_rows: unknown kind");
+}
+
+static int fold_nblk(int64_t kind, int64_t Sq) {
+  return kind == OB_FOLD_DKDV ? ob_fold_kv_nblk((int)Sq)
+                              : ob_fold_q_nblk((int)Sq);
+}
+
+// blocks in the launch of `kind` for Z = B*nh heads (padding included)
+extern "C" int64_t ob_flash_fold_grid(int64_t kind, int64_t Sq, int64_t Z) {
+  return (int64_t)ob_fold_grid(fold_nblk(kind, Sq), (int)Z);
+}
+
+// linear block id -> (z, block); returns 1, or 0 for a padding id
+extern "C" int ob_flash_fold_id(int64_t kind, int64_t Sq, int64_t Z,
+                                int64_t id, int64_t* z, int64_t* block) {
+  int blk, zz;
+  const bool ok =
+      ob_fold_id((unsigned)id, fold_nblk(kind, Sq), (int)Z, &blk, &zz);
+  *z = zz;
+  *block = blk;
+  return ok ? 1 : 0;
 }
 
 // D[z][q] = sum_d dO[q,d] * O[q,d]: runs before either backward family

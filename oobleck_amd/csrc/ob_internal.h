@@ -181,6 +181,10 @@ int ob_flash_bwd_nt_bf16(const void* qkv, const void* dO, const void* lse,
                          const void* D, void* dqkv, void* dbias_qkv,
                          int64_t B, int64_t Sq, int64_t H, int64_t nh,
                          float scale, void* stream);
+int ob_flash_bwd_nt_d_bf16(const void* qkv, const void* O, const void* dO,
+                           const void* lse, void* D_ws, void* dqkv,
+                           void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
+                           int64_t nh, float scale, void* stream);
 }
 // hipBLASLt path for plain GEMMs (ob_blaslt.hip); returns -1 when the
 // heuristic offers no algo (caller falls back to the hand-written path)

@@ -1018,14 +1018,12 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   if (flash_nt) {
     float* Dbuf = g_ws.t1;
     const float* lseP = st + l->o_p;
-    if (OB_PROF(OB_PF_FLASH_BWD, stream,
-                ob_flash_dsum_bf16(am, DATT, Dbuf, B, Sq, H, nh, stream)))
-      return 1;
+    // the dq kernel forms D = rowsum(dO * O) into Dbuf for the dkdv kernel;
     // also adds the b_qkv grad (column sums of DQKV) from its accumulators
     if (OB_PROF(OB_PF_FLASH_BWD, stream,
-                ob_flash_bwd_nt_bf16(qkv, DATT, lseP, Dbuf, DQKV,
-                                     g + bp.b_qkv, B, Sq, H, nh, scale,
-                                     stream)))
+                ob_flash_bwd_nt_d_bf16(qkv, am, DATT, lseP, Dbuf, DQKV,
+                                       g + bp.b_qkv, B, Sq, H, nh, scale,
+                                       stream)))
       return 1;
   } else if (use_flash(l)) {
     const int64_t BSH = BS * H;

@@ -95,6 +95,26 @@ def bwd_new(bias=None):
         nh, scale, stream()))
 
 
+def dsum():
+    check(ext.ob_flash_dsum_bf16(ptr(O), ptr(dO), ptr(D), B, S, H, nh,
+                                 stream()))
+
+
+def dsum_bwd_new(bias=None):
+    dsum()
+    bwd_new(bias)
+
+
+D_ws = torch.empty_like(D)
+
+
+def bwd_new_d(bias=None):
+    # dq forms D from O and dO itself and hands it to dkdv through D_ws
+    check(ext.ob_flash_bwd_nt_d_bf16(
+        ptr(qkv), ptr(O), ptr(dO), ptr(lse), ptr(D_ws), ptr(dqkv), ptr(bias),
+        B, S, H, nh, scale, stream()))
+
+
 O_old = torch.empty_like(O)
 fwd_old()
 O_old.copy_(O)
@@ -107,11 +127,19 @@ bwd_new()
 torch.cuda.synchronize()
 print(f"nt outputs bit-identical: fwd {torch.equal(O, O_old)} "
       f"bwd {torch.equal(dqkv, dq_old)}")
+dqkv.zero_()
+bwd_new_d()
+torch.cuda.synchronize()
+print(f"D in-kernel bit-identical: D {torch.equal(D_ws, D)} "
+      f"bwd {torch.equal(dqkv, dq_old)}")
 rows = [("fwd  transpose + v4          ", fwd_old),
         ("fwd  nt                      ", fwd_new),
         ("bwd  3 transposes + dkdv + dq", bwd_old),
         ("bwd  nt (dkdv + dq)          ", bwd_new),
         ("bwd  old + colsum(dqkv)      ", lambda: bwd_old(True)),
-        ("bwd  nt + bias in-kernel     ", lambda: bwd_new(dbias))]
+        ("bwd  nt + bias in-kernel     ", lambda: bwd_new(dbias)),
+        ("dsum alone                   ", dsum),
+        ("dsum + bwd nt + bias         ", lambda: dsum_bwd_new(dbias)),
+        ("bwd  nt, D in-kernel, + bias ", lambda: bwd_new_d(dbias))]
 for name, fn in rows:
     print(f"{name} {timeit(fn)*1e3:8.1f} us")
