@@ -298,6 +298,17 @@ int ob_gemm_bf16(int transA, int transB, int64_t M, int64_t N, int64_t K,
                  int64_t n1, int64_t n2,
                  const void* bias, const void* residual, int out_kind,
                  int splitk, void* stream);
+/* Host-only query (no GPU call): the route ob_gemm_bf16 takes for a call.
+ * aligned16: A/B bases 16-byte aligned and their batch strides multiples of
+ * 8.  env_mask: bit 0 OB_NO_BLASLT, bit 1 OB_BF16_NOGLDS, bit 2
+ * OB_BF16_NO256; force: the OB_BF16_FORCE string or null.
+ * out[5] = {hipBLASLt is tried first, kernel (0 generic, 1 glds 128x128,
+ * 2 256-row, 3 256x256 8-phase; the fallback when hipBLASLt is tried),
+ * N tile, generic kernel's edge guard, split-K}. */
+int ob_gemm_bf16_route(int transA, int transB, int64_t M, int64_t N, int64_t K,
+                       int64_t n1, int64_t n2, int out_kind, int splitk,
+                       float beta, int aligned16, int env_mask,
+                       const char* force, int32_t* out);
 
 /* Fused causal flash attention on packed bf16 qkv [B, Sq, 3H] (head_dim 64,
  * Sq % 128 == 0) without transposed operand copies: the kernels read the

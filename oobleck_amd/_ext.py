@@ -136,6 +136,9 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
                                         i64, i64, i64, i64, i64, i64, i64,
                                         i64, i64, i64, i64, f32, f32, i32,
                                         i32, vp, i64]
+    lib.ob_gemm_bf16_route.argtypes = [i32, i32, i64, i64, i64, i64, i64, i32,
+                                       i32, f32, i32, i32, ctypes.c_char_p,
+                                       ctypes.POINTER(ctypes.c_int32)]
     lib.ob_profile_enable.argtypes = [i32]
     lib.ob_profile_enable.restype = None
     lib.ob_profile_reset.argtypes = []

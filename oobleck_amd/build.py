@@ -9,6 +9,7 @@ PKG_DIR = pathlib.Path(__file__).resolve().parent
 SO_PATH = PKG_DIR / "libob_stage.so"
 SOURCES = [PKG_DIR / "csrc" / "ob_kernels.hip",
            PKG_DIR / "csrc" / "ob_kernels_bf16.hip",
+           PKG_DIR / "csrc" / "ob_gemm_bf16.hip",
            PKG_DIR / "csrc" / "ob_flash_bf16.hip",
            PKG_DIR / "csrc" / "ob_blaslt.hip",
            PKG_DIR / "csrc" / "ob_optim.hip",
@@ -17,6 +18,8 @@ SOURCES = [PKG_DIR / "csrc" / "ob_kernels.hip",
 HEADERS = [PKG_DIR.parent / "include" / "oobleck_stage.h",
            PKG_DIR / "csrc" / "ob_internal.h",
            PKG_DIR / "csrc" / "ob_flash_fold.h",
+           PKG_DIR / "csrc" / "ob_bf16.h",
+           PKG_DIR / "csrc" / "ob_gemm_route.h",
            PKG_DIR / "csrc" / "ob_philox.h"]
 
 

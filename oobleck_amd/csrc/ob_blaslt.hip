@@ -1,6 +1,6 @@
 // ob_blaslt.hip — hipBLASLt path for the PLAIN GEMMs of the hot path.
 //
-// The hand-written MFMA kernels (ob_kernels_bf16.hip) carry every FUSED
+// The hand-written MFMA kernels (ob_gemm_bf16.hip) carry every FUSED
 // op (bias/residual epilogues, flash attention, LN, CE); the plain
 // library GEMMs — dX (activation grads), the bias-free lm_head family,
 // and the TN weight-grad GEMMs (beta=1 accumulation straight into the

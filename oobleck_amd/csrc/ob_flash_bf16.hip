@@ -11,7 +11,7 @@
 //      bit-for-bit tests and the OB_FLASH_TR=0 path; see the section header.
 //
 // v_mfma_f32_32x32x16_bf16 fragment layout the kernels rely on (pinned by
-// tests/test_gpu_bf16.py; ob_kernels_bf16.hip derives it), il = lane&31,
+// tests/test_gpu_bf16.py; ob_gemm_bf16.hip derives it), il = lane&31,
 // kh = lane>>5:
 //   A: lane holds A[i = il][k = 8*kh + j], j = 0..7 (one ds_read_b128 of a
 //      [row][k] image)
@@ -59,6 +59,7 @@
 // prefetch alone only turns those stalls into dependency stalls; blocks are
 // 4 waves because the per-tile barrier makes a block wait for its longest
 // causal diagonal.
+#include "ob_bf16.h"
 #include "ob_internal.h"
 #include "ob_flash_fold.h"
 
@@ -69,30 +70,6 @@ using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
 
 static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-__device__ __forceinline__ float bf2f(__bf16 h) { return (float)h; }
-
-__device__ __forceinline__ unsigned bf_bits(__bf16 h) {
-  return (unsigned)__builtin_bit_cast(unsigned short, h);
-}
-__device__ __forceinline__ __bf16 bits_bf(unsigned u) {
-  return __builtin_bit_cast(__bf16, (unsigned short)(u & 0xffffu));
-}
-
-__device__ __forceinline__ __bf16 bf_extract(const uint4& v, int j) {
-  // j is a compile-time constant at every call site (unrolled loops)
-  const unsigned word = (j < 2) ? v.x : (j < 4) ? v.y : (j < 6) ? v.z : v.w;
-  return bits_bf((j & 1) ? (word >> 16) : word);
-}
-
-__device__ __forceinline__ uint4 bf_pack8(const float* v) {
-  uint4 o;
-  o.x = bf_bits((__bf16)v[0]) | (bf_bits((__bf16)v[1]) << 16);
-  o.y = bf_bits((__bf16)v[2]) | (bf_bits((__bf16)v[3]) << 16);
-  o.z = bf_bits((__bf16)v[4]) | (bf_bits((__bf16)v[5]) << 16);
-  o.w = bf_bits((__bf16)v[6]) | (bf_bits((__bf16)v[7]) << 16);
-  return o;
-}
 
 __device__ __forceinline__ unsigned bf_pk2(float a, float b) {
   return bf_bits((__bf16)a) | (bf_bits((__bf16)b) << 16);

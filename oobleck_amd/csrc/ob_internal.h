@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 
 #include "../../include/oobleck_stage.h"
 
@@ -27,6 +28,18 @@ int ob_fail(const char* fmt, ...);
       return ob_fail("%s:%d: launch: %s", __FILE__, __LINE__,         \
                      hipGetErrorString(e_));                          \
   } while (0)
+
+// Environment switches.  Call sites keep the result in a function-local
+// static const, so each switch is read once per process.  A default-off
+// flag is set by '1', a default-on flag is cleared by '0'.
+inline bool ob_env_flag(const char* name, bool dflt) {
+  const char* e = getenv(name);
+  return (e && e[0] == (dflt ? '0' : '1')) ? !dflt : dflt;
+}
+inline int ob_env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 // ---------------------------------------------------------------------------
 // In-step profiler (state in ob_layer.hip).  When enabled (ob_profile_enable,
@@ -113,7 +126,8 @@ int ob_embed_bwd_drop(const ob_drop_key& key, int bf16, const int64_t* ids,
                       int64_t Sq, int64_t H, void* stream);
 
 // bf16-path launchers (defined in ob_kernels_bf16.hip; the flash family
-// and ob_transpose_bf16_b in ob_flash_bf16.hip)
+// and ob_transpose_bf16_b in ob_flash_bf16.hip; the GEMMs, below, in
+// ob_gemm_bf16.hip)
 extern "C" {
 int ob_f32_to_bf16_t_ld(const void* x, void* y, int64_t rows, int64_t cols,
                         int64_t out_ld, void* stream);
@@ -208,21 +222,33 @@ extern "C" int ob_gemm_lt_f32(int tA, int tB, int64_t M, int64_t N,
                               int64_t lda, const void* B, int64_t ldb,
                               float beta, void* C, int64_t ldc,
                               void* stream);
-extern "C" int ob_gemm_bf16_nt_8ph(const void* A, const void* B, void* C,
-                                   const void* bias, const void* residual,
-                                   int64_t M, int64_t N, int64_t K,
-                                   int64_t lda, int64_t ldb, int64_t ldc,
-                                   int64_t sA1, int64_t sA2, int64_t sB1,
-                                   int64_t sB2, int64_t sC1, int64_t sC2,
-                                   int64_t n1, int64_t n2, float alpha,
-                                   float beta, int out_kind, int splitk,
-                                   void* stream, int64_t Mr);
-// fast NT glds dispatch (interior 128-tiled M/N; Mr = store-row guard)
-int ob_gemm_bf16_nt_dispatch(const void* A, const void* B, void* C,
-                             const void* bias, const void* residual,
-                             int64_t M, int64_t N, int64_t K, int64_t lda,
-                             int64_t ldb, int64_t ldc, int64_t sA1,
-                             int64_t sA2, int64_t sB1, int64_t sB2,
-                             int64_t sC1, int64_t sC2, int64_t n1, int64_t n2,
-                             float alpha, float beta, int out_kind, int splitk,
-                             void* stream, int64_t Mr);
+// ---------------------------------------------------------------------------
+// bf16 GEMM call (ob_gemm_bf16.hip): C = alpha * op(A) op(B) (+ bias)
+// (+ residual) (+ beta * C) over an n1 x n2 batch.  Leading dims and batch
+// strides are in elements.  The defaults are the layer's unbatched NT linear
+// (A [M,K], B [N,K], bf16 out).
+struct ob_bf16_gemm {
+  const void* A = nullptr;
+  const void* B = nullptr;
+  void* C = nullptr;
+  const void* bias = nullptr;      // fp32 [N]
+  const void* residual = nullptr;  // bf16, C's layout
+  int64_t M = 0, N = 0, K = 0;
+  int64_t lda = 0, ldb = 0, ldc = 0;
+  int64_t sA1 = 0, sA2 = 0, sB1 = 0, sB2 = 0, sC1 = 0, sC2 = 0;
+  int64_t n1 = 1, n2 = 1;
+  float alpha = 1.f, beta = 0.f;
+  int transA = 0, transB = 1;
+  int out_kind = 0;  // BF_OUT_*: 0 bf16, 1 f32, 2 f32 atomicAdd
+  int splitk = 1;    // > 1 needs out_kind 2
+  int64_t Mr = 0;    // NT dispatchers only: rows >= Mr are not stored
+  void* stream = nullptr;
+};
+// checks, routes (ob_gemm_route.h) and launches; ignores Mr (stores M rows)
+int ob_gemm_bf16_run(const ob_bf16_gemm& g);
+// the hand-written NT kernels, unconditionally.  glds: M, N % 128, K % 32;
+// nt256: M % 256, N % BN, BN in {128, 256}, K % 64; 8ph: M, N % 256,
+// K % 64.  All: 16-byte aligned bases and strides.
+int ob_gemm_bf16_nt_dispatch(const ob_bf16_gemm& g);
+int ob_gemm_bf16_nt256_dispatch(const ob_bf16_gemm& g, int BN);
+int ob_gemm_bf16_nt_8ph_dispatch(const ob_bf16_gemm& g);

@@ -507,10 +507,7 @@ extern "C" int ob_gemm_f32(int transA, int transB, int64_t M, int64_t N,
   const bool edge = (M % GEMM_BM) || (N % BN) || (K % GEMM_BK);
   // 2-phase double-buffered pipeline when the K loop is deep enough to
   // overlap (ob_GEMM_V1=1 in the environment falls back, for A/B runs).
-  static const bool force_v1 = [] {
-    const char* e = getenv("OB_GEMM_V1");
-    return e && e[0] == '1';
-  }();
+  static const bool force_v1 = ob_env_flag("OB_GEMM_V1", false);
   // P2 wins on interior shapes (+3..27%) but loses on edge shapes
   // (lm_head N=50257: 113.7->103.1 TF measured) - gate on !edge.
   const bool p2 = !force_v1 && !edge && K >= 2 * GEMM_BK;
@@ -544,10 +541,7 @@ extern "C" int ob_gemm_f32(int transA, int transB, int64_t M, int64_t N,
   // fp32 TN glds-direct kernel: measured perf-neutral on the dW shapes
   // (85 TF either way — fp32 dW is tail/occupancy-bound, not
   // staging-bound), so it stays opt-in for experiments.
-  static const bool tn_glds = [] {
-    const char* e = getenv("OB_F32_TN_GLDS");
-    return e && e[0] == '1';
-  }();
+  static const bool tn_glds = ob_env_flag("OB_F32_TN_GLDS", false);
   if (tn_glds && transA && !transB && atomic && !edge && BN == 128 &&
       (reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) %
               16 == 0 &&

@@ -194,7 +194,7 @@ struct ob_layer {
           o_u = 0, o_g = 0, o_logits = 0, o_lse = 0;
   // bf16 mode (d.dtype == 1): weight shadows in plain + transposed layouts
   // so every GEMM operand has k contiguous in memory (see
-  // ob_kernels_bf16.hip header).  The stash keeps its fp32-sized offsets
+  // ob_gemm_bf16.hip header).  The stash keeps its fp32-sized offsets
   // and bf16 data occupies the first half of each region (2x overcommit,
   // traded for zero layout churn; memory is plentiful at 288 GB).
   __bf16* shadows = nullptr;
@@ -234,11 +234,8 @@ static bool flash_eligible(const ob_layer_desc* d, float attn_pdrop = 0.f) {
   // attention dropout takes the materialized-P path (fused flash dropout is
   // the follow-up)
   if (attn_pdrop > 0.f) return false;
-  static const bool off = [] {
-    const char* e = getenv("OB_BF16_FLASH");
-    return e && e[0] == '0';
-  }();
-  return !off && d->dtype == 1 && d->n_embd / d->n_head == 64 &&
+  static const bool on = ob_env_flag("OB_BF16_FLASH", true);
+  return on && d->dtype == 1 && d->n_embd / d->n_head == 64 &&
          d->seq_len % 128 == 0;
 }
 
@@ -247,10 +244,7 @@ static bool flash_eligible(const ob_layer_desc* d, float attn_pdrop = 0.f) {
 // b_qkv bias grad comes from the backward kernels' accumulators.
 // OB_FLASH_TR=0 (read once) keeps the transposes + old kernels + colsum.
 static bool flash_tr() {
-  static const bool on = [] {
-    const char* e = getenv("OB_FLASH_TR");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = ob_env_flag("OB_FLASH_TR", true);
   return on;
 }
 
@@ -533,10 +527,7 @@ static int gemm(int tA, int tB, int64_t M, int64_t N, int64_t K, float alpha,
                 int atomic, int splitk, void* stream) {
   // plain (unbatched, no fused epilogue) fp32 GEMMs to hipBLASLt —
   // covers the dW family too (it accumulates through beta=1)
-  static const bool no_lt = [] {
-    const char* e = getenv("OB_NO_BLASLT");
-    return e && e[0] == '1';
-  }();
+  static const bool no_lt = ob_env_flag("OB_NO_BLASLT", false);
   if (!no_lt && !bias && !R && !atomic && splitk <= 1 && n1 == 1 &&
       n2 == 1 && M * N >= 512 * 512) {
     const int r = ob_gemm_lt_f32(tA, tB, M, N, K, alpha, A, lda, B, ldb,
@@ -565,10 +556,7 @@ static int gemm_dx_splitk(int tB, int64_t M, int64_t N, int64_t K,
                           float alpha, const float* A, int64_t lda,
                           const float* B, int64_t ldb, float* C, int64_t ldc,
                           void* stream) {
-  static const bool no_lt = [] {
-    const char* e = getenv("OB_NO_BLASLT");
-    return e && e[0] == '1';
-  }();
+  static const bool no_lt = ob_env_flag("OB_NO_BLASLT", false);
   if (!no_lt) {
     const int r = ob_gemm_lt_f32(0, tB, M, N, K, alpha, A, lda, B, ldb, 0.f,
                                  C, ldc, stream);
@@ -703,18 +691,30 @@ static int final_forward(ob_layer* l, int slot, const float* in, float* out,
 // bf16 mixed-precision path (d.dtype == 1): bf16 activations + bf16 MFMA
 // GEMMs with fp32 accumulate, fp32 master weights/biases/LN params, fp32
 // grads.  Weight operands come from the plain/transposed shadows so every
-// GEMM stages its operands with k contiguous (see ob_kernels_bf16.hip).
+// GEMM stages its operands with k contiguous (see ob_gemm_bf16.hip).
 // ---------------------------------------------------------------------------
 
-static int gemm_bf(int tA, int tB, int64_t M, int64_t N, int64_t K,
-                   float alpha, const void* A, int64_t lda, int64_t sA1,
-                   int64_t sA2, const void* B, int64_t ldb, int64_t sB1,
-                   int64_t sB2, void* C, int64_t ldc, int64_t sC1,
-                   int64_t sC2, int64_t n1, int64_t n2, const float* bias,
-                   const void* R, int out_kind, int splitk, void* stream) {
-  return ob_gemm_bf16(tA, tB, M, N, K, alpha, A, lda, sA1, sA2, B, ldb, sB1,
-                      sB2, 0.f, C, ldc, sC1, sC2, n1, n2, bias, R, out_kind,
-                      splitk, stream);
+// unbatched NT linear, bf16 out: out[M,N] = in[M,K] @ W[N,K]^T (+ bias)
+// (+ res).  The forward projections, the dX GEMMs, lm_head and d_lnout.
+static int linear_bf(const void* in, int64_t M, int64_t K, const void* W,
+                     int64_t N, const float* bias, const void* res, void* out,
+                     void* stream) {
+  ob_bf16_gemm g;
+  g.A = in, g.B = W, g.C = out, g.bias = bias, g.residual = res;
+  g.M = M, g.N = N, g.K = K, g.lda = K, g.ldb = K, g.ldc = N;
+  g.stream = stream;
+  return ob_gemm_bf16_run(g);
+}
+
+// the non-flash attention matmuls: one [M,K] x [K,N] product per (batch,
+// head); the caller names the three operands' leading dims and strides
+static ob_bf16_gemm attn_gemm(int tA, int tB, int64_t M, int64_t N, int64_t K,
+                              float alpha, int64_t B, int64_t nh,
+                              void* stream) {
+  ob_bf16_gemm g;
+  g.transA = tA, g.transB = tB, g.M = M, g.N = N, g.K = K, g.alpha = alpha;
+  g.n1 = B, g.n2 = nh, g.stream = stream;
+  return g;
 }
 
 // weight-grad GEMM for bf16: materialize X^T / dY^T (cheap HBM transpose)
@@ -726,29 +726,28 @@ static int dw_bf16_ws(const __bf16* act, int64_t actw, const __bf16* dY,
   // direct TN via hipBLASLt with beta=1 accumulation into the fp32 flat
   // grads: no transpose materialization, no atomics (measured 694 TF on
   // the fc dW shape vs 436 for transpose + atomic NT)
-  static const bool no_lt = [] {
-    const char* e = getenv("OB_NO_BLASLT");
-    return e && e[0] == '1';
-  }();
+  static const bool no_lt = ob_env_flag("OB_NO_BLASLT", false);
   if (!no_lt && ldc == dyw) {
     const int r = ob_gemm_lt(1, 0, actw, dyw, BS, 1.f, act, actw, dY, dyw,
                              1.f, gout, ldc, 1, stream);
     if (r >= 0) return r;
   }
-  if ((actw % 128) || (dyw % 128) || (BS % 128))
-    return gemm_bf(1, 0, actw, dyw, BS, 1.f, act, actw, 0, 0, dY, dyw, 0, 0,
-                   gout, ldc, 0, 0, 1, 1, nullptr, nullptr, 2,
-                   pick_splitk(actw, dyw, BS), stream);
+  // gout[actw,dyw] += act^T dY, atomically, K = BS split to fill the chip
+  ob_bf16_gemm g;
+  g.C = gout, g.M = actw, g.N = dyw, g.K = BS, g.ldc = ldc;
+  g.out_kind = 2, g.splitk = pick_splitk(actw, dyw, BS), g.stream = stream;
+  if ((actw % 128) || (dyw % 128) || (BS % 128)) {
+    g.transA = 1, g.transB = 0;
+    g.A = act, g.lda = actw, g.B = dY, g.ldb = dyw;
+    return ob_gemm_bf16_run(g);
+  }
   __bf16* XT = (__bf16*)w1;
   __bf16* DYT = (__bf16*)w2;
   if (ob_transpose_bf16(act, XT, BS, actw, stream)) return 1;
   if (ob_transpose_bf16(dY, DYT, BS, dyw, stream)) return 1;
-  return gemm_bf(0, 1, actw, dyw, BS, 1.f, XT, BS, 0, 0, DYT, BS, 0, 0, gout,
-                 ldc, 0, 0, 1, 1, nullptr, nullptr, 2,
-                 pick_splitk(actw, dyw, BS), stream);
+  g.A = XT, g.lda = BS, g.B = DYT, g.ldb = BS;
+  return ob_gemm_bf16_run(g);
 }
-
-static bool use_flash(const ob_layer* l) { return l->flash; }
 
 static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
                               __bf16* out, void* stream) {
@@ -772,12 +771,11 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
     return 1;
   __bf16* qkv = (__bf16*)(st + l->o_qkv);
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
-              gemm_bf(0, 1, BS, 3 * H, H, 1.f, ln1, H, 0, 0,
-                      sh + l->sh_qkv_t, H, 0, 0, qkv, 3 * H, 0, 0, 1, 1,
-                      p + bp.b_qkv, nullptr, 0, 1, stream)))
+              linear_bf(ln1, BS, H, sh + l->sh_qkv_t, 3 * H, p + bp.b_qkv,
+                        nullptr, qkv, stream)))
     return 1;
   __bf16* am = (__bf16*)(st + l->o_attnm);
-  if (use_flash(l) && flash_tr()) {
+  if (l->flash && flash_tr()) {
     // the fused kernel writes O and the per-row LSE (stored where the
     // materialized-P path keeps P)
     float* lseP = st + l->o_p;
@@ -785,7 +783,7 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
                 ob_flash_fwd_nt_bf16(qkv, am, lseP, B, Sq, H, nh,
                                      1.f / sqrtf((float)hd), stream)))
       return 1;
-  } else if (use_flash(l)) {
+  } else if (l->flash) {
     // OB_FLASH_TR=0: V^T materialization (workspace, transient within this
     // call) feeding the kernel that takes a transposed V
     __bf16* VTw = (__bf16*)g_ws.t2;
@@ -800,11 +798,11 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
       return 1;
   } else {
     __bf16* P = (__bf16*)(st + l->o_p);
-    if (OB_PROF(OB_PF_ATTN_MAT, stream,
-                gemm_bf(0, 1, Sq, Sq, hd, 1.f, qkv, 3 * H, Sq * 3 * H, hd,
-                        qkv + H, 3 * H, Sq * 3 * H, hd, P, Sq, nh * Sq * Sq,
-                        Sq * Sq, B, nh, nullptr, nullptr, 0, 1, stream)))
-      return 1;
+    ob_bf16_gemm qk = attn_gemm(0, 1, Sq, Sq, hd, 1.f, B, nh, stream);
+    qk.A = qkv, qk.lda = 3 * H, qk.sA1 = Sq * 3 * H, qk.sA2 = hd;
+    qk.B = qkv + H, qk.ldb = 3 * H, qk.sB1 = Sq * 3 * H, qk.sB2 = hd;
+    qk.C = P, qk.ldc = Sq, qk.sC1 = nh * Sq * Sq, qk.sC2 = Sq * Sq;
+    if (OB_PROF(OB_PF_ATTN_MAT, stream, ob_gemm_bf16_run(qk))) return 1;
     if (OB_PROF(OB_PF_ATTN_MAT, stream,
                 ob_softmax_causal_fwd_bf16(P, B * nh, Sq,
                                            1.f / sqrtf((float)hd), stream)))
@@ -819,17 +817,16 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
         return 1;
       Pv = (const __bf16*)g_ws.pd_f;
     }
-    if (OB_PROF(OB_PF_ATTN_MAT, stream,
-                gemm_bf(0, 0, Sq, hd, Sq, 1.f, Pv, Sq, nh * Sq * Sq, Sq * Sq,
-                        qkv + 2 * H, 3 * H, Sq * 3 * H, hd, am, H, Sq * H,
-                        hd, B, nh, nullptr, nullptr, 0, 1, stream)))
-      return 1;
+    ob_bf16_gemm pv = attn_gemm(0, 0, Sq, hd, Sq, 1.f, B, nh, stream);
+    pv.A = Pv, pv.lda = Sq, pv.sA1 = nh * Sq * Sq, pv.sA2 = Sq * Sq;
+    pv.B = qkv + 2 * H, pv.ldb = 3 * H, pv.sB1 = Sq * 3 * H, pv.sB2 = hd;
+    pv.C = am, pv.ldc = H, pv.sC1 = Sq * H, pv.sC2 = hd;
+    if (OB_PROF(OB_PF_ATTN_MAT, stream, ob_gemm_bf16_run(pv))) return 1;
   }
   __bf16* hmid = (__bf16*)(st + l->o_hmid);
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
-              gemm_bf(0, 1, BS, H, H, 1.f, am, H, 0, 0, sh + l->sh_ap_t, H,
-                      0, 0, hmid, H, 0, 0, 1, 1, p + bp.b_attnproj,
-                      dR ? nullptr : x, 0, 1, stream)))
+              linear_bf(am, BS, H, sh + l->sh_ap_t, H, p + bp.b_attnproj,
+                        dR ? nullptr : x, hmid, stream)))
     return 1;
   // residual dropout: the GEMM wrote the biased projection only
   if (dR &&
@@ -845,18 +842,16 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
     return 1;
   __bf16* u = (__bf16*)(st + l->o_u);
   if (OB_PROF(OB_PF_FC_FWD, stream,
-              gemm_bf(0, 1, BS, 4 * H, H, 1.f, ln2, H, 0, 0, sh + l->sh_fc_t,
-                      H, 0, 0, u, 4 * H, 0, 0, 1, 1, p + bp.b_fc, nullptr, 0,
-                      1, stream)))
+              linear_bf(ln2, BS, H, sh + l->sh_fc_t, 4 * H, p + bp.b_fc,
+                        nullptr, u, stream)))
     return 1;
   __bf16* gact = (__bf16*)(st + l->o_g);
   if (OB_PROF(OB_PF_ELEM, stream,
               ob_gelu_fwd_bf16(u, gact, BS * 4 * H, stream)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
-              gemm_bf(0, 1, BS, H, 4 * H, 1.f, gact, 4 * H, 0, 0,
-                      sh + l->sh_mp_t, 4 * H, 0, 0, out, H, 0, 0, 1, 1,
-                      p + bp.b_mlpproj, dR ? nullptr : hmid, 0, 1, stream)))
+              linear_bf(gact, BS, 4 * H, sh + l->sh_mp_t, H,
+                        p + bp.b_mlpproj, dR ? nullptr : hmid, out, stream)))
     return 1;
   if (dR &&
       OB_PROF(OB_PF_ELEM, stream,
@@ -888,9 +883,8 @@ static int final_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   __bf16* logits = (__bf16*)(st + l->o_logits);
   // N = v_pad (zero-padded shadow rows -> padded logits are exactly 0)
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
-              gemm_bf(0, 1, BS, l->v_pad, H, 1.f, lnf, H, 0, 0,
-                      l->shadows + l->sh_lm, H, 0, 0, logits, l->v_pad, 0, 0,
-                      1, 1, nullptr, nullptr, 0, 1, stream)))
+              linear_bf(lnf, BS, H, l->shadows + l->sh_lm, l->v_pad, nullptr,
+                        nullptr, logits, stream)))
     return 1;
   OB_HIP(hipMemsetAsync(out, 0, sizeof(float), S(stream)));
   if (OB_PROF(OB_PF_CE, stream,
@@ -955,9 +949,8 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     OB_SIDE_FENCE(S(stream), g_side.stream);  // dm2 ready
   }
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              gemm_bf(0, 1, BS, 4 * H, H, 1.f, dmlp, H, 0, 0, sh + l->sh_mp,
-                      H, 0, 0, DY4, 4 * H, 0, 0, 1, 1, nullptr, nullptr, 0,
-                      1, stream)))
+              linear_bf(dmlp, BS, H, sh + l->sh_mp, 4 * H, nullptr, nullptr,
+                        DY4, stream)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DW, side,
               dw_bf16_ws(gact, 4 * H, dmlp, H, BS, g + bp.w_mlpproj, H,
@@ -974,9 +967,8 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
                          g_ws.s2, side)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              gemm_bf(0, 1, BS, H, 4 * H, 1.f, DY4, 4 * H, 0, 0,
-                      sh + l->sh_fc, 4 * H, 0, 0, DLN, H, 0, 0, 1, 1,
-                      nullptr, nullptr, 0, 1, stream)))
+              linear_bf(DY4, BS, 4 * H, sh + l->sh_fc, H, nullptr, nullptr,
+                        DLN, stream)))
     return 1;
   // ln2 backward takes the residual straight from dout (din = dout + v,
   // no entry copy) and sums both streams it holds in registers: dout
@@ -1001,9 +993,8 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   }
   OB_SIDE_FENCE(S(stream), g_side.stream);  // din post-ln2-bwd (dm1 ready)
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              gemm_bf(0, 1, BS, H, H, 1.f, dap, H, 0, 0, sh + l->sh_ap, H, 0,
-                      0, DATT, H, 0, 0, 1, 1, nullptr, nullptr, 0, 1,
-                      stream)))
+              linear_bf(dap, BS, H, sh + l->sh_ap, H, nullptr, nullptr, DATT,
+                        stream)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DW, side,
               dw_bf16_ws(am, H, dap, H, BS, g + bp.w_attnproj, H, g_ws.s1,
@@ -1014,7 +1005,7 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   hipEvent_t ev_din_done = side_evt();
   OB_HIP(hipEventRecord(ev_din_done, g_side.stream));
   // ---- attention core ----
-  const bool flash_nt = use_flash(l) && flash_tr();
+  const bool flash_nt = l->flash && flash_tr();
   if (flash_nt) {
     float* Dbuf = g_ws.t1;
     const float* lseP = st + l->o_p;
@@ -1025,7 +1016,7 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
                                        g + bp.b_qkv, B, Sq, H, nh, scale,
                                        stream)))
       return 1;
-  } else if (use_flash(l)) {
+  } else if (l->flash) {
     const int64_t BSH = BS * H;
     __bf16* QTw = (__bf16*)g_ws.t1;
     __bf16* KTw = QTw + BSH;
@@ -1052,12 +1043,12 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
                                   DQKV, B, Sq, H, nh, scale, stream)))
       return 1;
   } else {
-    if (OB_PROF(OB_PF_ATTN_MAT, stream,
-                gemm_bf(0, 1, Sq, Sq, hd, 1.f, DATT, H, Sq * H, hd,
-                        qkv + 2 * H, 3 * H, Sq * 3 * H, hd, DP, Sq,
-                        nh * Sq * Sq, Sq * Sq, B, nh, nullptr, nullptr, 0, 1,
-                        stream)))
-      return 1;
+    // dPd = dO V^T
+    ob_bf16_gemm dp = attn_gemm(0, 1, Sq, Sq, hd, 1.f, B, nh, stream);
+    dp.A = DATT, dp.lda = H, dp.sA1 = Sq * H, dp.sA2 = hd;
+    dp.B = qkv + 2 * H, dp.ldb = 3 * H, dp.sB1 = Sq * 3 * H, dp.sB2 = hd;
+    dp.C = DP, dp.ldc = Sq, dp.sC1 = nh * Sq * Sq, dp.sC2 = Sq * Sq;
+    if (OB_PROF(OB_PF_ATTN_MAT, stream, ob_gemm_bf16_run(dp))) return 1;
     // attention dropout: DP holds dPd.  Regenerate Pd for dV, mask dPd into
     // dP in place, then the softmax backward runs on the stored P.
     const __bf16* Pv = P;
@@ -1075,23 +1066,19 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     if (OB_PROF(OB_PF_ATTN_MAT, stream,
                 ob_softmax_causal_bwd_bf16(P, DP, B * nh, Sq, stream)))
       return 1;
-    if (OB_PROF(OB_PF_ATTN_MAT, stream,
-                gemm_bf(0, 0, Sq, hd, Sq, scale, DP, Sq, nh * Sq * Sq,
-                        Sq * Sq, qkv + H, 3 * H, Sq * 3 * H, hd, DQKV, 3 * H,
-                        Sq * 3 * H, hd, B, nh, nullptr, nullptr, 0, 1,
-                        stream)))
-      return 1;
-    if (OB_PROF(OB_PF_ATTN_MAT, stream,
-                gemm_bf(1, 0, Sq, hd, Sq, scale, DP, Sq, nh * Sq * Sq,
-                        Sq * Sq, qkv, 3 * H, Sq * 3 * H, hd, DQKV + H, 3 * H,
-                        Sq * 3 * H, hd, B, nh, nullptr, nullptr, 0, 1,
-                        stream)))
-      return 1;
-    if (OB_PROF(OB_PF_ATTN_MAT, stream,
-                gemm_bf(1, 0, Sq, hd, Sq, 1.f, Pv, Sq, nh * Sq * Sq, Sq * Sq,
-                        DATT, H, Sq * H, hd, DQKV + 2 * H, 3 * H, Sq * 3 * H,
-                        hd, B, nh, nullptr, nullptr, 0, 1, stream)))
-      return 1;
+    // dQ = scale dS K, dK = scale dS^T Q, dV = Pd^T dO into DQKV's thirds
+    ob_bf16_gemm dq = attn_gemm(0, 0, Sq, hd, Sq, scale, B, nh, stream);
+    dq.A = DP, dq.lda = Sq, dq.sA1 = nh * Sq * Sq, dq.sA2 = Sq * Sq;
+    dq.B = qkv + H, dq.ldb = 3 * H, dq.sB1 = Sq * 3 * H, dq.sB2 = hd;
+    dq.C = DQKV, dq.ldc = 3 * H, dq.sC1 = Sq * 3 * H, dq.sC2 = hd;
+    if (OB_PROF(OB_PF_ATTN_MAT, stream, ob_gemm_bf16_run(dq))) return 1;
+    ob_bf16_gemm dk = dq;
+    dk.transA = 1, dk.B = qkv, dk.C = DQKV + H;
+    if (OB_PROF(OB_PF_ATTN_MAT, stream, ob_gemm_bf16_run(dk))) return 1;
+    ob_bf16_gemm dv = dk;
+    dv.alpha = 1.f, dv.A = Pv, dv.C = DQKV + 2 * H;
+    dv.B = DATT, dv.ldb = H, dv.sB1 = Sq * H, dv.sB2 = hd;
+    if (OB_PROF(OB_PF_ATTN_MAT, stream, ob_gemm_bf16_run(dv))) return 1;
   }
   // ---- QKV projection ----
   OB_SIDE_FENCE(S(stream), g_side.stream);  // DQKV ready
@@ -1104,9 +1091,8 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
                          g_ws.s1, g_ws.s2, side)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              gemm_bf(0, 1, BS, H, 3 * H, 1.f, DQKV, 3 * H, 0, 0,
-                      sh + l->sh_qkv, 3 * H, 0, 0, DLN, H, 0, 0, 1, 1,
-                      nullptr, nullptr, 0, 1, stream)))
+              linear_bf(DQKV, BS, 3 * H, sh + l->sh_qkv, H, nullptr, nullptr,
+                        DLN, stream)))
     return 1;
   // ln1 backward accumulates into din: wait for the side's din readers
   OB_HIP(hipStreamWaitEvent(S(stream), ev_din_done, 0));
@@ -1146,10 +1132,7 @@ static int final_backward_bf16(ob_layer* l, int slot, const float* dout,
     void* const side = (void*)g_side.stream;
     // direct TN via hipBLASLt: M = V with lda = v_pad skips the pad
     // rows entirely (no store guard, no 826 MB logits transpose)
-    static const bool no_lt = [] {
-      const char* e = getenv("OB_NO_BLASLT");
-      return e && e[0] == '1';
-    }();
+    static const bool no_lt = ob_env_flag("OB_NO_BLASLT", false);
     int r = -1;
     if (!no_lt)
       r = OB_PROF(OB_PF_GEMM_DW, side,
@@ -1161,19 +1144,18 @@ static int final_backward_bf16(ob_layer* l, int slot, const float* dout,
       __bf16* LNT = (__bf16*)g_ws.s2;
       if (ob_transpose_bf16(logits, DLT, BS, l->v_pad, side)) return 1;
       if (ob_transpose_bf16(lnf, LNT, BS, H, side)) return 1;
-      if (OB_PROF(OB_PF_GEMM_DW, side,
-                  ob_gemm_bf16_nt_dispatch(DLT, LNT, g + 2 * H, nullptr,
-                                           nullptr, l->v_pad, H, BS, BS, BS,
-                                           H, 0, 0, 0, 0, 0, 0, 1, 1, 1.f,
-                                           0.f, 2, 2, side, V)))
+      ob_bf16_gemm dw;
+      dw.A = DLT, dw.lda = BS, dw.B = LNT, dw.ldb = BS;
+      dw.C = g + 2 * H, dw.ldc = H, dw.M = l->v_pad, dw.N = H, dw.K = BS;
+      dw.out_kind = 2, dw.splitk = 2, dw.Mr = V, dw.stream = side;
+      if (OB_PROF(OB_PF_GEMM_DW, side, ob_gemm_bf16_nt_dispatch(dw)))
         return 1;
     }
   }
   // d_lnout: K = v_pad (padded dlogits cols and shadow^T cols are zero)
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              gemm_bf(0, 1, BS, H, l->v_pad, 1.f, logits, l->v_pad, 0, 0,
-                      l->shadows + l->sh_lm_t, l->v_pad, 0, 0, DLN, H, 0, 0,
-                      1, 1, nullptr, nullptr, 0, 1, stream)))
+              linear_bf(logits, BS, l->v_pad, l->shadows + l->sh_lm_t, H,
+                        nullptr, nullptr, DLN, stream)))
     return 1;
   if (OB_PROF(OB_PF_LN, stream,
               ob_layernorm_bwd_bf16(x, p + 0, st + l->o_mean1,

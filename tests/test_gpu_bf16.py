@@ -121,6 +121,82 @@ def test_gemm_bf16_batched_strided():
 
 
 # ---------------------------------------------------------------------------
+# The two NT families the small ob_gemm_bf16 shapes above never route to, at
+# the smallest shapes inside what the production dispatch sends them
+# (M % 256, K % 64; K >= 1024 for the 256-row kernel).  Same tolerances as
+# above: fp32 out 1e-3, bf16 out 2e-2, against torch fp32 on the bf16 inputs.
+# ---------------------------------------------------------------------------
+
+def _nt_case(M, N, K):
+    A, B = rb(M, K, seed=11), rb(N, K, seed=12)  # asymmetric operands
+    return A, B, A.float() @ B.float().t()
+
+
+def _nt_out(M, N, out_kind):
+    if out_kind == 0:
+        return torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
+    return torch.zeros(M, N, device=DEV, dtype=torch.float32)
+
+
+def _tol(out_kind):
+    return dict(rtol=2e-2, atol=2e-2) if out_kind == 0 else \
+        dict(rtol=1e-3, atol=1e-3)
+
+
+def gemm_nt_8ph(A, B, C, M, N, K, *, out_kind, splitk=1, bias=None,
+                residual=None):
+    from oobleck_amd._ext import check, get_ext
+    check(get_ext().ob_gemm_bf16_nt_8ph(
+        ptr(A), ptr(B), ptr(C), ptr(bias), ptr(residual), M, N, K, K, K, N,
+        0, 0, 0, 0, 0, 0, 1, 1, 1.0, 0.0, out_kind, splitk, stream(), M),
+        "gemm_bf16_nt_8ph")
+
+
+@requires_gpu
+@pytest.mark.parametrize("out_kind,splitk", [(0, 1), (1, 1), (2, 2)])
+@pytest.mark.parametrize("M,N,K", [(256, 256, 768), (512, 256, 1024)])
+def test_gemm_bf16_nt_8ph_parity(M, N, K, out_kind, splitk):
+    A, B, ref = _nt_case(M, N, K)
+    C = _nt_out(M, N, out_kind)  # zeroed for the atomic split-K sum
+    gemm_nt_8ph(A, B, C, M, N, K, out_kind=out_kind, splitk=splitk)
+    torch.cuda.synchronize()
+    torch.testing.assert_close(C.float(), ref, **_tol(out_kind))
+
+
+@requires_gpu
+def test_gemm_bf16_nt_8ph_bias_residual():
+    M, N, K = 256, 256, 768
+    A, B, ref = _nt_case(M, N, K)
+    bias = torch.randn(N, device=DEV)
+    R = rb(M, N, seed=13)
+    C = _nt_out(M, N, 0)
+    gemm_nt_8ph(A, B, C, M, N, K, out_kind=0, bias=bias, residual=R)
+    torch.cuda.synchronize()
+    torch.testing.assert_close(C.float(), ref + bias + R.float(), **_tol(0))
+
+
+@requires_gpu
+@pytest.mark.parametrize("out_kind", [0, 1])
+@pytest.mark.parametrize("force,BN,M,N,K", [("n2", 256, 256, 256, 1024),
+                                            ("n1", 128, 256, 128, 1024)])
+def test_gemm_bf16_nt256_parity(monkeypatch, force, BN, M, N, K, out_kind):
+    from oobleck_amd._ext import get_ext
+    r = (ctypes.c_int32 * 5)()
+    assert get_ext().ob_gemm_bf16_route(0, 1, M, N, K, 1, 1, out_kind, 1, 0.0,
+                                        1, 0, force.encode(), r) == 0
+    assert (r[1], r[2]) == (2, BN)  # the 256-row kernel at this N tile
+    A, B, ref = _nt_case(M, N, K)
+    C = _nt_out(M, N, out_kind)
+    # OB_BF16_FORCE is read on every call
+    monkeypatch.setenv("OB_BF16_FORCE", force)
+    gemm_bf16(A, B, C, transB=1, M=M, N=N, K=K, lda=K, ldb=K, ldc=N,
+              out_kind=out_kind)
+    monkeypatch.delenv("OB_BF16_FORCE")
+    torch.cuda.synchronize()
+    torch.testing.assert_close(C.float(), ref, **_tol(out_kind))
+
+
+# ---------------------------------------------------------------------------
 # bf16 layer-path parity vs the fp32 oracle.  bf16 has an 8-bit mantissa:
 # tolerances are the documented bf16 bound (BASELINE.md "separate documented
 # tolerance for the bf16 path"): loss rel 2e-2; activation outputs rel/abs
