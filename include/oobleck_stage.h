@@ -94,8 +94,11 @@ enum {
 typedef struct {
   float embd_pdrop;     /* EMBED layers; each probability in [0,1) */
   float resid_pdrop;    /* BLOCK layers, sites 2 and 3 */
-  float attn_pdrop;     /* BLOCK layers, site 1; > 0 takes the materialized-P
-                           attention path (no flash) */
+  float attn_pdrop;     /* BLOCK layers, site 1.  A flash-eligible layer draws
+                           the masks inside the flash kernels
+                           (ob_flash_*_nt_drop_bf16); with OB_FLASH_DROP=0 or
+                           OB_FLASH_TR=0 in the environment, > 0 takes the
+                           materialized-P attention path instead */
   int32_t layer_id;     /* 0 <= layer_id < 2^24 */
   uint64_t seed;
 } ob_dropout_desc;
@@ -104,6 +107,11 @@ typedef struct {
  * ob_layer_create: the same kernels are launched and nothing else. */
 int ob_layer_create_ex(const ob_layer_desc* desc, const ob_dropout_desc* drop,
                        ob_layer_t* out);
+
+/* 1 when the layer's attention runs the fused flash kernels (bf16 BLOCK,
+ * head_dim 64, seq_len % 128 == 0, and for attn_pdrop > 0 neither
+ * OB_FLASH_DROP=0 nor OB_FLASH_TR=0), 0 otherwise.  Host-only. */
+int ob_layer_uses_flash(ob_layer_t l);
 
 /* Training mode (default 1).  0 makes dropout inert (eval): forwards run
  * today's dropout-free path and do not advance the tick. */
@@ -331,6 +339,23 @@ int ob_flash_bwd_nt_d_bf16(const void* qkv, const void* O, const void* dO,
                            const void* lse, void* D_ws, void* dqkv,
                            void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
                            int64_t nh, float scale, void* stream);
+/* ob_flash_fwd_nt_bf16 / ob_flash_bwd_nt_d_bf16 with attention dropout drawn
+ * inside the kernels: site OB_DROP_ATTN of (seed, layer_id, tick, p), element
+ * index into the full [B*nh, Sq, Sq] square as the dropout section above
+ * defines it; no mask or P is stored.  The forward's LSE is that of the
+ * undropped P and O = (P * factor) V; the backward must be given the
+ * forward's key.  Same shape rules as the plain entries; also p in [0,1) and
+ * B*nh*Sq*Sq <= 2^34.  p == 0 launches the plain kernels. */
+int ob_flash_fwd_nt_drop_bf16(const void* qkv, void* O, void* lse, int64_t B,
+                              int64_t Sq, int64_t H, int64_t nh, float scale,
+                              uint64_t seed, int32_t layer_id, uint64_t tick,
+                              float p, void* stream);
+int ob_flash_bwd_nt_d_drop_bf16(const void* qkv, const void* O, const void* dO,
+                                const void* lse, void* D_ws, void* dqkv,
+                                void* dbias_qkv, int64_t B, int64_t Sq,
+                                int64_t H, int64_t nh, float scale,
+                                uint64_t seed, int32_t layer_id, uint64_t tick,
+                                float p, void* stream);
 /* Host-only queries of the block -> work mapping of the three kernels above
  * (no GPU call).  kind: 0 forward, 1 dq, 2 dkdv.
  * rows: unit = wave 0..3 (forward, dq) or wave pair 0..1 (dkdv) of `block`

@@ -54,6 +54,7 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
                                        ctypes.POINTER(ObDropoutDesc),
                                        ctypes.POINTER(vp)]
     lib.ob_layer_set_training.argtypes = [vp, i32]
+    lib.ob_layer_uses_flash.argtypes = [vp]
     lib.ob_layer_set_dropout_tick.argtypes = [vp, u64]
     # (seed, layer_id, site, tick, p) select the mask of every dropout entry
     key = [u64, i32, i32, u64, f32]
@@ -154,6 +155,12 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
                                          i64, i64, f32, vp]
     lib.ob_flash_bwd_nt_d_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64,
                                            i64, i64, i64, f32, vp]
+    # (seed, layer_id, tick, p): the site is always DROP_ATTN
+    lib.ob_flash_fwd_nt_drop_bf16.argtypes = [vp, vp, vp, i64, i64, i64, i64,
+                                              f32, u64, i32, u64, f32, vp]
+    lib.ob_flash_bwd_nt_d_drop_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp,
+                                                i64, i64, i64, i64, f32, u64,
+                                                i32, u64, f32, vp]
     p64 = ctypes.POINTER(ctypes.c_int64)
     lib.ob_flash_fold_rows.argtypes = [i64, i64, i64, i64, p64, p64, p64]
     lib.ob_flash_fold_grid.argtypes = [i64, i64, i64]

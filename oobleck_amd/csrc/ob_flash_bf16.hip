@@ -4,7 +4,9 @@
 // Two families of the same three kernels (forward, dK/dV, dQ):
 //   1. production: k_flash_fwd_nt / k_flash_bwd_dkdv_nt / k_flash_bwd_dq_nt
 //      (ob_flash_fwd_nt_bf16, ob_flash_bwd_nt_bf16 and, with D formed in
-//      the dq kernel, ob_flash_bwd_nt_d_bf16), plus k_flash_dsum;
+//      the dq kernel, ob_flash_bwd_nt_d_bf16), plus k_flash_dsum; their
+//      kDrop instantiations apply attention dropout in registers
+//      (ob_flash_fwd_nt_drop_bf16, ob_flash_bwd_nt_d_drop_bf16);
 //   2. their transposed-operand twins k_flash_fwd_bf16_v4 /
 //      k_flash_bwd_dkdv_s / k_flash_bwd_dq_v3 (ob_flash_fwd_bf16,
 //      ob_flash_bwd_bf16) fed by k_transpose_bf16_b — the reference of the
@@ -62,6 +64,7 @@
 #include "ob_bf16.h"
 #include "ob_internal.h"
 #include "ob_flash_fold.h"
+#include "ob_philox.h"
 
 #include <cmath>
 
@@ -157,6 +160,46 @@ __device__ __forceinline__ bf16x8 nt_tr_frag(const __bf16* tile, int lane,
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
+// Attention dropout (kDrop instantiations).  The mask
+// is ob_philox.h's, site OB_DROP_ATTN: element e = (z*S + q)*S + kv of the
+// full [B*nh, S, S] square, word e & 3 of ob_drop_words(key, e >> 2), and
+// ob_drop_factor's rule (word >= thr keeps, kept values times key.scale).
+// No mask touches memory: a Philox call covers four consecutive, 4-aligned
+// kv of one q row, S % 4 == 0, and e < 2^34 (checked by the entries), so
+//   e >> 2 = (z*S + q) * (S/4) + (kv >> 2)   fits 32 bits.
+// The kernels keep the keep bits of a tile in one register and apply
+// `bit ? key.scale : 0` where ob_drop_factor would.  Only elements at or
+// below the diagonal ever reach a product that matters: masked P is 0
+// before the factor multiplies it.  The mask code is plain VALU (plus one
+// quad exchange in dkdv) under wave-uniform control and holds no
+// transposed read and no barrier.
+//
+// forward / dq orientation: a lane holds q = myq and, per 32-kv sub-tile u,
+// the kv rows kv0 + 32u + acc_row(r, kh): group g = r>>2 is the 4-aligned
+// run kv0 + 32u + 8g + 4kh, i.e. exactly one Philox call, counter
+// crow + 8u + 2g with crow = drop_crow(z, S, myq, kh) + kv0/4.  Bit 16u + r
+// = keep of sub-tile u, element r.  8 calls per lane and 64-kv tile, in a
+// rolled loop: unrolled, their temporaries push the kernels into scratch.
+__device__ __forceinline__ uint32_t drop_crow(int z, int Sq, int q, int kh) {
+  return (uint32_t)(z * Sq + q) * (uint32_t)(Sq >> 2) + (uint32_t)kh;
+}
+__device__ __forceinline__ uint32_t drop_bits_q(const ob_drop_key& key,
+                                                uint32_t crow) {
+  uint32_t bits = 0;
+#pragma unroll 1
+  for (int i = 0; i < 8; ++i) {  // i = 4u + g
+    const ob_philox4 w = ob_drop_words(key, crow + 2 * i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      bits |= (uint32_t)(w.w[j] >= key.thr) << (4 * i + j);
+  }
+  return bits;
+}
+__device__ __forceinline__ float drop_factor_bit(const ob_drop_key& key,
+                                                 uint32_t bits, int i) {
+  return ((bits >> i) & 1u) ? key.scale : 0.f;
+}
+
 // Forward: 4 waves x 32 q-rows = 128 q-rows per block; KVBLK = 64.
 //   * K and V tiles STAGED IN LDS, double-buffered, shared by the 4 waves
 //     (two coalesced 16 B chunks per thread and tile instead of each wave's
@@ -177,9 +220,14 @@ __device__ __forceinline__ bf16x8 nt_tr_frag(const __bf16* tile, int lane,
 //     tiles wholly below the diagonal skip the causal mask.
 // vbuf is staged from V rows like kbuf from K rows; the PV B fragments are
 // its columns.
+// kDrop: m, l and the stored LSE come from the undropped P (the backward
+// recomputes P from them); PV multiplies Pd = P * factor, formed in fp32
+// before bf_dance packs it.  `key` is unused without kDrop.
+template <bool kDrop>
 __global__ __launch_bounds__(256, 3) void k_flash_fwd_nt(
     const __bf16* __restrict__ qkv, __bf16* __restrict__ Obase,
-    float* __restrict__ lse, int Sq, int H, int nh, int Z, float scale) {
+    float* __restrict__ lse, int Sq, int H, int nh, int Z, float scale,
+    ob_drop_key key) {
   __shared__ __attribute__((aligned(16))) __bf16 kbuf[2][64 * 64];
   __shared__ __attribute__((aligned(16))) __bf16 vbuf[2][64 * 64];
   __shared__ float bcast[128];
@@ -234,6 +282,12 @@ __global__ __launch_bounds__(256, 3) void k_flash_fwd_nt(
   float m = -INFINITY, l = 0.f;
   for (int kvt = 0; kvt < ntiles; ++kvt) {
     const int kv0 = kvt * 64;
+    // drawn (by the waves still active) before the staging loads take
+    // their registers
+    [[maybe_unused]] uint32_t keep = 0;
+    if constexpr (kDrop)
+      if (kvt < mytiles)
+        keep = drop_bits_q(key, drop_crow(z, Sq, myq, kh) + (kv0 >> 2));
     if (kvt + 1 < ntiles) stage((kvt + 1) & 1, kv0 + 64);
     const bool active = kvt < mytiles;  // kv0 <= q0 + 31, wave-uniform
     if (active) {
@@ -299,6 +353,10 @@ __global__ __launch_bounds__(256, 3) void k_flash_fwd_nt(
                    ((ps[4] + ps[5]) + (ps[6] + ps[7]));
       psum += __shfl_xor(psum, 32, 64);
       l += psum;
+      if constexpr (kDrop) {
+#pragma unroll
+        for (int r = 0; r < 32; ++r) sv[r] *= drop_factor_bit(key, keep, r);
+      }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const bf16x8 pa = bf_dance(sv + t * 8);
@@ -331,9 +389,42 @@ extern "C" int ob_flash_fwd_nt_bf16(const void* qkv, void* O, void* lse,
   if (H / nh != 64) return ob_fail("flash_fwd_nt: head_dim must be 64");
   if (Sq % 128) return ob_fail("flash_fwd_nt: S must be a multiple of 128");
   const int Z = (int)(B * nh);
-  k_flash_fwd_nt<<<ob_fold_grid(ob_fold_q_nblk((int)Sq), Z), 256, 0,
-                   S(stream)>>>((const __bf16*)qkv, (__bf16*)O, (float*)lse,
-                                (int)Sq, (int)H, (int)nh, Z, scale);
+  k_flash_fwd_nt<false><<<ob_fold_grid(ob_fold_q_nblk((int)Sq), Z), 256, 0,
+                          S(stream)>>>((const __bf16*)qkv, (__bf16*)O,
+                                       (float*)lse, (int)Sq, (int)H, (int)nh,
+                                       Z, scale, ob_drop_key{});
+  OB_LAUNCH_CHECK();
+  return 0;
+}
+
+// shape and key checks shared by the two dropout entries
+static int drop_args_ok(const char* who, int64_t B, int64_t Sq, int64_t H,
+                        int64_t nh, float p) {
+  if (nh <= 0 || H / nh != 64) return ob_fail("%s: head_dim must be 64", who);
+  if (Sq <= 0 || Sq % 128)
+    return ob_fail("%s: S must be a multiple of 128", who);
+  if (!ob_drop_p_ok(p)) return ob_fail("%s: p must be in [0,1)", who);
+  if (B <= 0 || B * nh * Sq * Sq > ((int64_t)1 << 34))
+    return ob_fail("%s: B*nh*S*S exceeds the 2^34 mask elements", who);
+  return 0;
+}
+
+// ob_flash_fwd_nt_bf16 with attention dropout (site OB_DROP_ATTN) applied
+// to P before PV; p == 0 is the plain kernel.
+extern "C" int ob_flash_fwd_nt_drop_bf16(const void* qkv, void* O, void* lse,
+                                         int64_t B, int64_t Sq, int64_t H,
+                                         int64_t nh, float scale,
+                                         uint64_t seed, int32_t layer_id,
+                                         uint64_t tick, float p,
+                                         void* stream) {
+  if (drop_args_ok("flash_fwd_nt_drop", B, Sq, H, nh, p)) return 1;
+  if (p == 0.f)
+    return ob_flash_fwd_nt_bf16(qkv, O, lse, B, Sq, H, nh, scale, stream);
+  const int Z = (int)(B * nh);
+  k_flash_fwd_nt<true><<<ob_fold_grid(ob_fold_q_nblk((int)Sq), Z), 256, 0,
+                         S(stream)>>>(
+      (const __bf16*)qkv, (__bf16*)O, (float*)lse, (int)Sq, (int)H, (int)nh,
+      Z, scale, ob_drop_make_key(seed, layer_id, OB_DROP_ATTN, tick, p));
   OB_LAUNCH_CHECK();
   return 0;
 }
@@ -363,11 +454,30 @@ extern "C" int ob_flash_fwd_nt_bf16(const void* qkv, void* O, void* lse,
 // tile qt+2 into this buffer.
 // dbias (fp32 [3H], may be null): += column sums of this block's dK and dV
 // tiles, taken from the fp32 accumulators after `scale`, before rounding.
-__global__ __launch_bounds__(256, 3) void k_flash_bwd_dkdv_nt(
+// kDrop: dV accumulates Pd^T dO, dK accumulates dS^T Q with
+// dS = P * (factor*dP - D).  Role 0 draws the mask and hands it to role 1
+// inside the P exchange, as the sign bit of the fp32 P it writes to xch
+// (P >= 0; a dropped P goes out negative): no extra LDS, no second Philox.
+// Role 0 feeds dV with keep ? P*scale : 0; role 1 reads |x| as P and the
+// sign as the keep bit.  Here a lane holds ONE kv column and 16 q rows, so
+// the four lanes of a quad (il & ~3) need the same 16 Philox calls, one per
+// q row, and each lane uses word il & 3 of every one.  Lane j of the quad
+// makes the 4 calls of rows r = 4g + j, packs the 16 keep bits (bit
+// 4g + word) and the quad exchanges the packed registers: a quarter of the
+// Philox work of every lane drawing its own 16 calls, which measured 387 us
+// against 280 us for the whole backward at (8, 12, 1024)
+// (profiles/flash_drop_probe.log).
+// Launch bound: the kDrop instantiation is bound to 2 waves/SIMD.  The
+// plain body already sits at 167 VGPRs, most of them hoisted per-lane row
+// and exchange addresses; with the mask on top the compiler takes 211, and
+// under bound 3 it spills the dV/dK B fragments across the exchange instead
+// (76 B/lane of scratch and more).
+template <bool kDrop>
+__global__ __launch_bounds__(256, kDrop ? 2 : 3) void k_flash_bwd_dkdv_nt(
     const __bf16* __restrict__ qkv, const __bf16* __restrict__ dO,
     const float* __restrict__ lse, const float* __restrict__ D,
     __bf16* __restrict__ dqkv, float* __restrict__ dbias, int Sq, int H,
-    int nh, int Z, float scale) {
+    int nh, int Z, float scale, ob_drop_key key) {
   __shared__ float xch[2][2][32 * 32];  // [buffer][pair][P tile]
   __shared__ __attribute__((aligned(16))) __bf16 qbuf[2][32 * 64];
   __shared__ __attribute__((aligned(16))) __bf16 obuf[2][32 * 64];
@@ -392,6 +502,7 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dkdv_nt(
   const int kv0 = ob_fold_kv_row0(Sq, blk, pair);
   const int mykv = kv0 + il;
   const int myqt0 = ob_fold_kv_pair_first(kv0);
+  [[maybe_unused]] const uint32_t sq4 = (uint32_t)(Sq >> 2);
 
   const __bf16* KV = role ? Vp : Kp;
   bf16x8 of[4];
@@ -419,6 +530,34 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dkdv_nt(
 
   for (int qt = qt0; qt < nqt; ++qt) {
     const int q0 = qt * 32;
+    // bit r: keep of element r (q row q0 + acc_row(r, kh), column mykv);
+    // drawn by role 0 before the staging loads take their registers
+    [[maybe_unused]] uint32_t keep = 0;
+    if constexpr (kDrop) {
+      if (role == 0 && qt >= myqt0) {  // wave-uniform
+        // Philox counter of q row q0 + 4*kh at this lane's kv quad
+        const uint32_t c0 = (uint32_t)(z * Sq + q0 + 4 * kh) * sq4 +
+                            (uint32_t)(mykv >> 2);
+        uint32_t mine = 0;  // rows r = 4g + (il & 3): bit 4g + word
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const ob_philox4 w4 =
+              ob_drop_words(key, c0 + (uint32_t)((il & 3) + 8 * g) * sq4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            mine |= (uint32_t)(w4.w[j] >= key.thr) << (4 * g + j);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          // quad lane j drew rows 4g + j; take this lane's word of each
+          const uint32_t theirs =
+              (uint32_t)__shfl((int)mine, (lane & ~3) | j, 64) >> (il & 3);
+#pragma unroll
+          for (int g = 0; g < 4; ++g)
+            keep |= ((theirs >> (4 * g)) & 1u) << (4 * g + j);
+        }
+      }
+    }
     if (qt + 1 < nqt) stage((qt + 1) & 1, q0 + 32);
     // wave-uniform: pair 1 idles (staging and the barrier only) until the
     // loop reaches its diagonal, q0 + 31 >= kv0.  Each wave meets exactly
@@ -456,7 +595,13 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dkdv_nt(
         const bool ok = q0 + qoff >= mykv;
         const float lse_q = __shfl(lse_t, qoff, 64);
         pv[r] = ok ? __expf(own[r] * scale - lse_q) : 0.f;
-        ptile[qoff * 32 + il] = pv[r];
+        if constexpr (kDrop) {
+          const bool kept = (keep >> r) & 1u;
+          ptile[qoff * 32 + il] = kept ? pv[r] : -pv[r];
+          pv[r] = kept ? pv[r] * key.scale : 0.f;
+        } else {
+          ptile[qoff * 32 + il] = pv[r];
+        }
       }
     }
     __syncthreads();
@@ -466,8 +611,15 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dkdv_nt(
       for (int r = 0; r < 16; ++r) {
         const int qoff = acc_row(r, kh);
         const float d_q = __shfl(d_t, qoff, 64);
-        // dS = P * (dP - D); masked entries have P == 0 already
-        pv[r] = ptile[qoff * 32 + il] * (own[r] - d_q);
+        if constexpr (kDrop) {
+          // dS = P * (factor*dP - D): |x| is P, a set sign bit says dropped
+          const float x = ptile[qoff * 32 + il];
+          const float f = __builtin_signbit(x) ? 0.f : key.scale;
+          pv[r] = __builtin_fabsf(x) * (f * own[r] - d_q);
+        } else {
+          // dS = P * (dP - D); masked entries have P == 0 already
+          pv[r] = ptile[qoff * 32 + il] * (own[r] - d_q);
+        }
       }
     }
 #pragma unroll
@@ -530,13 +682,16 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dkdv_nt(
 // ((c0+c4)+(c2+c6)) + ((c1+c5)+(c3+c7))), so D is bit-identical to that
 // kernel's: the bf16 x bf16 products are exact in fp32, so contraction to
 // fma cannot move a bit either.
-template <bool kFormD>
+// kDrop: D = rowsum(dO * O) is unchanged (sum_k P_k m_k dPd_k = dO . O
+// when O = Pd V); dP = factor * (V . dO) and dS = P * (dP - D) with the
+// undropped P.  Mask bits as in the forward.
+template <bool kFormD, bool kDrop>
 __global__ __launch_bounds__(256, 3) void k_flash_bwd_dq_nt(
     const __bf16* __restrict__ qkv, const __bf16* __restrict__ dO,
     const float* __restrict__ lse, const float* __restrict__ D,
     const __bf16* __restrict__ O, float* __restrict__ Dout,
     __bf16* __restrict__ dqkv, float* __restrict__ dbias, int Sq, int H,
-    int nh, int Z, float scale) {
+    int nh, int Z, float scale, ob_drop_key key) {
   __shared__ __attribute__((aligned(16))) __bf16 kbuf[2][64 * 64];
   __shared__ __attribute__((aligned(16))) __bf16 vbuf[2][64 * 64];
   __shared__ float red[4 * 64];
@@ -614,6 +769,12 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dq_nt(
   f32x16 dq0 = {}, dq1 = {};
   for (int kvt = 0; kvt < ntiles; ++kvt) {
     const int kv0 = kvt * 64;
+    // drawn (by the waves still active) before the staging loads take
+    // their registers
+    [[maybe_unused]] uint32_t keep = 0;
+    if constexpr (kDrop)
+      if (kvt < mytiles)
+        keep = drop_bits_q(key, drop_crow(z, Sq, myq, kh) + (kv0 >> 2));
     if (kvt + 1 < ntiles) stage((kvt + 1) & 1, kv0 + 64);
     // wave-uniform causal skip: kv0 <= q0 + 31
     const bool active = kvt < mytiles;
@@ -648,8 +809,15 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dq_nt(
         const bool ok1 = kv + 32 <= myq;
         const float pa = ok0 ? __expf(s0[r] * scale - mylse) : 0.f;
         const float pb = ok1 ? __expf(s1[r] * scale - mylse) : 0.f;
-        dsv[r] = ok0 ? pa * (p0[r] - myD) : 0.f;
-        dsv[16 + r] = ok1 ? pb * (p1[r] - myD) : 0.f;
+        if constexpr (kDrop) {
+          const float f0 = drop_factor_bit(key, keep, r);
+          const float f1 = drop_factor_bit(key, keep, 16 + r);
+          dsv[r] = ok0 ? pa * (f0 * p0[r] - myD) : 0.f;
+          dsv[16 + r] = ok1 ? pb * (f1 * p1[r] - myD) : 0.f;
+        } else {
+          dsv[r] = ok0 ? pa * (p0[r] - myD) : 0.f;
+          dsv[16 + r] = ok1 ? pb * (p1[r] - myD) : 0.f;
+        }
       }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
@@ -690,16 +858,17 @@ __global__ __launch_bounds__(256, 3) void k_flash_bwd_dq_nt(
   }
 }
 
+template <bool kDrop>
 static int launch_dkdv_nt(const void* qkv, const void* dO, const void* lse,
                           const void* D, void* dqkv, void* dbias_qkv,
                           int64_t B, int64_t Sq, int64_t H, int64_t nh,
-                          float scale, void* stream) {
+                          float scale, const ob_drop_key& key, void* stream) {
   const int Z = (int)(B * nh);
-  k_flash_bwd_dkdv_nt<<<ob_fold_grid(ob_fold_kv_nblk((int)Sq), Z), 256, 0,
-                        S(stream)>>>(
-      (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse,
-      (const float*)D, (__bf16*)dqkv, (float*)dbias_qkv, (int)Sq, (int)H,
-      (int)nh, Z, scale);
+  k_flash_bwd_dkdv_nt<kDrop>
+      <<<ob_fold_grid(ob_fold_kv_nblk((int)Sq), Z), 256, 0, S(stream)>>>(
+          (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse,
+          (const float*)D, (__bf16*)dqkv, (float*)dbias_qkv, (int)Sq, (int)H,
+          (int)nh, Z, scale, key);
   OB_LAUNCH_CHECK();
   return 0;
 }
@@ -711,15 +880,16 @@ extern "C" int ob_flash_bwd_nt_bf16(const void* qkv, const void* dO,
                                     float scale, void* stream) {
   if (H / nh != 64) return ob_fail("flash_bwd_nt: head_dim must be 64");
   if (Sq % 128) return ob_fail("flash_bwd_nt: S must be a multiple of 128");
-  if (launch_dkdv_nt(qkv, dO, lse, D, dqkv, dbias_qkv, B, Sq, H, nh, scale,
-                     stream))
+  if (launch_dkdv_nt<false>(qkv, dO, lse, D, dqkv, dbias_qkv, B, Sq, H, nh,
+                            scale, ob_drop_key{}, stream))
     return 1;
   const int Z = (int)(B * nh);
-  k_flash_bwd_dq_nt<false>
+  k_flash_bwd_dq_nt<false, false>
       <<<ob_fold_grid(ob_fold_q_nblk((int)Sq), Z), 256, 0, S(stream)>>>(
           (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse,
           (const float*)D, nullptr, nullptr, (__bf16*)dqkv,
-          (float*)dbias_qkv, (int)Sq, (int)H, (int)nh, Z, scale);
+          (float*)dbias_qkv, (int)Sq, (int)H, (int)nh, Z, scale,
+          ob_drop_key{});
   OB_LAUNCH_CHECK();
   return 0;
 }
@@ -735,14 +905,38 @@ extern "C" int ob_flash_bwd_nt_d_bf16(const void* qkv, const void* O,
   if (H / nh != 64) return ob_fail("flash_bwd_nt_d: head_dim must be 64");
   if (Sq % 128) return ob_fail("flash_bwd_nt_d: S must be a multiple of 128");
   const int Z = (int)(B * nh);
-  k_flash_bwd_dq_nt<true>
+  k_flash_bwd_dq_nt<true, false>
       <<<ob_fold_grid(ob_fold_q_nblk((int)Sq), Z), 256, 0, S(stream)>>>(
           (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse, nullptr,
           (const __bf16*)O, (float*)D_ws, (__bf16*)dqkv, (float*)dbias_qkv,
-          (int)Sq, (int)H, (int)nh, Z, scale);
+          (int)Sq, (int)H, (int)nh, Z, scale, ob_drop_key{});
   OB_LAUNCH_CHECK();
-  return launch_dkdv_nt(qkv, dO, lse, D_ws, dqkv, dbias_qkv, B, Sq, H, nh,
-                        scale, stream);
+  return launch_dkdv_nt<false>(qkv, dO, lse, D_ws, dqkv, dbias_qkv, B, Sq, H,
+                               nh, scale, ob_drop_key{}, stream);
+}
+
+// ob_flash_bwd_nt_d_bf16 for a forward that ran ob_flash_fwd_nt_drop_bf16
+// with the same key; p == 0 is the plain backward.
+extern "C" int ob_flash_bwd_nt_d_drop_bf16(
+    const void* qkv, const void* O, const void* dO, const void* lse,
+    void* D_ws, void* dqkv, void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
+    int64_t nh, float scale, uint64_t seed, int32_t layer_id, uint64_t tick,
+    float p, void* stream) {
+  if (drop_args_ok("flash_bwd_nt_d_drop", B, Sq, H, nh, p)) return 1;
+  if (p == 0.f)
+    return ob_flash_bwd_nt_d_bf16(qkv, O, dO, lse, D_ws, dqkv, dbias_qkv, B,
+                                  Sq, H, nh, scale, stream);
+  const ob_drop_key key =
+      ob_drop_make_key(seed, layer_id, OB_DROP_ATTN, tick, p);
+  const int Z = (int)(B * nh);
+  k_flash_bwd_dq_nt<true, true>
+      <<<ob_fold_grid(ob_fold_q_nblk((int)Sq), Z), 256, 0, S(stream)>>>(
+          (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse, nullptr,
+          (const __bf16*)O, (float*)D_ws, (__bf16*)dqkv, (float*)dbias_qkv,
+          (int)Sq, (int)H, (int)nh, Z, scale, key);
+  OB_LAUNCH_CHECK();
+  return launch_dkdv_nt<true>(qkv, dO, lse, D_ws, dqkv, dbias_qkv, B, Sq, H,
+                              nh, scale, key, stream);
 }
 
 // Host-only queries of the ob_flash_fold.h mapping (no GPU call), for the

@@ -35,9 +35,12 @@ struct Workspace {
   float* t2 = nullptr;     // also the bf16 transposed operands (t2: fwd V^T)
   float* s1 = nullptr;     // side-stream dW transpose buffers (bf16 as
   float* s2 = nullptr;     // floats): the dW family runs on g_side
-  // dropout only (never allocated without it).  pd_f belongs to the
-  // FORWARD (Pd = drop(P) feeding the PV GEMM): under pp1 overlap a forward
-  // runs beside a backward, so it shares nothing with the buffers below.
+  // dropout only (never allocated without it); pd_f / pd_b only for
+  // attention dropout on the materialized-P path (a flash layer regenerates
+  // its masks in the flash kernels and owns no [B*nh, S, S] buffer).  pd_f
+  // belongs to the FORWARD (Pd = drop(P) feeding the PV GEMM): under pp1
+  // overlap a forward runs beside a backward, so it shares nothing with the
+  // buffers below.
   // pd_b is the backward's regenerated Pd; dm1/dm2 hold the masked
   // projection grads, which the side-stream dW GEMMs read until the
   // end-of-call join (DATT/DLN are overwritten by the main stream earlier).
@@ -227,18 +230,6 @@ static ob_drop_key drop_key(const ob_layer* l, int slot, int site, float p) {
   return ob_drop_make_key(l->seed, l->layer_id, site, l->slot_tick[slot], p);
 }
 
-// flash applies when head_dim == 64 and S % 128 == 0 (GPT-2 small and
-// XL both qualify); OB_BF16_FLASH=0 falls back to the materialized-P
-// path.  Decided at create time: it sizes the stash.
-static bool flash_eligible(const ob_layer_desc* d, float attn_pdrop = 0.f) {
-  // attention dropout takes the materialized-P path (fused flash dropout is
-  // the follow-up)
-  if (attn_pdrop > 0.f) return false;
-  static const bool on = ob_env_flag("OB_BF16_FLASH", true);
-  return on && d->dtype == 1 && d->n_embd / d->n_head == 64 &&
-         d->seq_len % 128 == 0;
-}
-
 // The flash path reads its column-major MFMA operands from the row-major LDS
 // tiles (ob_flash_*_nt_bf16): no V^T / Q^T / K^T / dO^T copies, and the
 // b_qkv bias grad comes from the backward kernels' accumulators.
@@ -246,6 +237,26 @@ static bool flash_eligible(const ob_layer_desc* d, float attn_pdrop = 0.f) {
 static bool flash_tr() {
   static const bool on = ob_env_flag("OB_FLASH_TR", true);
   return on;
+}
+
+// Attention dropout inside the flash kernels (ob_flash_*_nt_drop_bf16).
+// OB_FLASH_DROP=0 (read once) sends attn_pdrop > 0 to the materialized-P
+// path instead, as before those kernels existed.
+static bool flash_drop() {
+  static const bool on = ob_env_flag("OB_FLASH_DROP", true);
+  return on;
+}
+
+// flash applies when head_dim == 64 and S % 128 == 0 (GPT-2 small and
+// XL both qualify); OB_BF16_FLASH=0 falls back to the materialized-P
+// path.  Decided at create time: it sizes the stash.
+static bool flash_eligible(const ob_layer_desc* d, float attn_pdrop = 0.f) {
+  // only the production kernels have a dropout variant, not the
+  // OB_FLASH_TR=0 twins
+  if (attn_pdrop > 0.f && !(flash_tr() && flash_drop())) return false;
+  static const bool on = ob_env_flag("OB_BF16_FLASH", true);
+  return on && d->dtype == 1 && d->n_embd / d->n_head == 64 &&
+         d->seq_len % 128 == 0;
 }
 
 // parameter offsets (canonical layout, oracle/gpt2_oracle.py::layer_param_spec)
@@ -421,8 +432,9 @@ static int layer_create(const ob_layer_desc* d, const ob_dropout_desc* drop,
     if (ws_ensure(&g_ws.bsh1, &g_ws.sz_bsh, need)) return 1;
     if (ws_ensure(&g_ws.bsh2, &g_ws.sz_bsh2, need)) return 1;
   }
-  // dropout workspaces (sized in floats; bf16 uses the first half)
-  if (l->p_attn > 0.f) {
+  // dropout workspaces (sized in floats; bf16 uses the first half); a flash
+  // layer draws its attention masks in the flash kernels and needs none
+  if (l->p_attn > 0.f && !l->flash) {
     if (ws_ensure(&g_ws.pd_f, &g_ws.sz_pd_f, Bm * nh * Sq * Sq)) return 1;
     if (ws_ensure(&g_ws.pd_b, &g_ws.sz_pd_b, Bm * nh * Sq * Sq)) return 1;
   }
@@ -442,6 +454,10 @@ extern "C" int ob_layer_create_ex(const ob_layer_desc* d,
                                   const ob_dropout_desc* drop,
                                   ob_layer_t* out) {
   return layer_create(d, drop, out);
+}
+
+extern "C" int ob_layer_uses_flash(ob_layer_t l) {
+  return l && l->flash ? 1 : 0;
 }
 
 extern "C" int ob_layer_set_training(ob_layer_t l, int on) {
@@ -779,9 +795,17 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
     // the fused kernel writes O and the per-row LSE (stored where the
     // materialized-P path keeps P)
     float* lseP = st + l->o_p;
-    if (OB_PROF(OB_PF_FLASH_FWD, stream,
-                ob_flash_fwd_nt_bf16(qkv, am, lseP, B, Sq, H, nh,
-                                     1.f / sqrtf((float)hd), stream)))
+    if (dA) {
+      // attention dropout inside the kernel: masks of this slot's tick
+      if (OB_PROF(OB_PF_FLASH_FWD, stream,
+                  ob_flash_fwd_nt_drop_bf16(qkv, am, lseP, B, Sq, H, nh,
+                                            1.f / sqrtf((float)hd), l->seed,
+                                            l->layer_id, l->slot_tick[slot],
+                                            l->p_attn, stream)))
+        return 1;
+    } else if (OB_PROF(OB_PF_FLASH_FWD, stream,
+                       ob_flash_fwd_nt_bf16(qkv, am, lseP, B, Sq, H, nh,
+                                            1.f / sqrtf((float)hd), stream)))
       return 1;
   } else if (l->flash) {
     // OB_FLASH_TR=0: V^T materialization (workspace, transient within this
@@ -808,7 +832,7 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
                                            1.f / sqrtf((float)hd), stream)))
       return 1;
     // attention dropout: stash keeps P, the PV GEMM reads Pd = drop(P) from
-    // the forward-only workspace (create_ex cleared `flash` for p_attn > 0)
+    // the forward-only workspace (only a non-flash layer gets here with dA)
     const __bf16* Pv = P;
     if (dA) {
       if (OB_PROF(OB_PF_ELEM, stream,
@@ -1011,10 +1035,19 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     const float* lseP = st + l->o_p;
     // the dq kernel forms D = rowsum(dO * O) into Dbuf for the dkdv kernel;
     // also adds the b_qkv grad (column sums of DQKV) from its accumulators
-    if (OB_PROF(OB_PF_FLASH_BWD, stream,
-                ob_flash_bwd_nt_d_bf16(qkv, am, DATT, lseP, Dbuf, DQKV,
-                                       g + bp.b_qkv, B, Sq, H, nh, scale,
-                                       stream)))
+    if (dA) {
+      // regenerates the masks the forward of this slot drew
+      if (OB_PROF(OB_PF_FLASH_BWD, stream,
+                  ob_flash_bwd_nt_d_drop_bf16(qkv, am, DATT, lseP, Dbuf, DQKV,
+                                              g + bp.b_qkv, B, Sq, H, nh,
+                                              scale, l->seed, l->layer_id,
+                                              l->slot_tick[slot], l->p_attn,
+                                              stream)))
+        return 1;
+    } else if (OB_PROF(OB_PF_FLASH_BWD, stream,
+                       ob_flash_bwd_nt_d_bf16(qkv, am, DATT, lseP, Dbuf, DQKV,
+                                              g + bp.b_qkv, B, Sq, H, nh,
+                                              scale, stream)))
       return 1;
   } else if (l->flash) {
     const int64_t BSH = BS * H;

@@ -140,6 +140,12 @@ class Layer:
                   f"refresh_weights layer {self.layer_id}")
             self._shadows_stale = False
 
+    @property
+    def uses_flash(self) -> bool:
+        """Whether this layer's attention runs the fused flash kernels
+        (decided when the layer was created)."""
+        return bool(get_ext().ob_layer_uses_flash(self._h))
+
     def train(self) -> None:
         """Training mode (the default): dropout masks are drawn."""
         check(get_ext().ob_layer_set_training(self._h, 1), "set_training")

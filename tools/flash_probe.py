@@ -4,6 +4,11 @@
 # under OB_FLASH_TR=0) vs the production `_nt` entry points.  Prints whether
 # the outputs are bit-identical, then one timing row per path.
 # Per-kernel times: run this file under a kernel trace (tools/kstats.py).
+#
+# --attn-pdrop P (0 < P < 1) adds the attention-dropout entries
+# (ob_flash_fwd_nt_drop_bf16 / ob_flash_bwd_nt_d_drop_bf16) next to the plain
+# ones.
+import argparse
 import ctypes
 import pathlib
 import sys
@@ -12,6 +17,11 @@ import torch
 
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent.parent))
 from oobleck_amd._ext import check, get_ext  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--attn-pdrop", type=float, default=0.0, metavar="P",
+                help="also time the dropout variants of the three kernels")
+args = ap.parse_args()
 
 B, nh, S, hd = 8, 12, 1024, 64
 H = nh * hd
@@ -115,6 +125,23 @@ def bwd_new_d(bias=None):
         B, S, H, nh, scale, stream()))
 
 
+# dropout key: any seed / layer / tick; the cost does not depend on them
+DROP_KEY = ((0xDEADBEEF << 32) | 0x1234567, 5, (1 << 32) + 3)
+
+
+def fwd_drop():
+    check(ext.ob_flash_fwd_nt_drop_bf16(
+        ptr(qkv), ptr(O), ptr(lse), B, S, H, nh, scale, DROP_KEY[0],
+        DROP_KEY[1], DROP_KEY[2], args.attn_pdrop, stream()))
+
+
+def bwd_drop(bias=None):
+    check(ext.ob_flash_bwd_nt_d_drop_bf16(
+        ptr(qkv), ptr(O), ptr(dO), ptr(lse), ptr(D_ws), ptr(dqkv), ptr(bias),
+        B, S, H, nh, scale, DROP_KEY[0], DROP_KEY[1], DROP_KEY[2],
+        args.attn_pdrop, stream()))
+
+
 O_old = torch.empty_like(O)
 fwd_old()
 O_old.copy_(O)
@@ -143,3 +170,10 @@ rows = [("fwd  transpose + v4          ", fwd_old),
         ("bwd  nt, D in-kernel, + bias ", lambda: bwd_new_d(dbias))]
 for name, fn in rows:
     print(f"{name} {timeit(fn)*1e3:8.1f} us")
+if args.attn_pdrop > 0.0:
+    fwd_drop()   # the dropout backward reads the dropout forward's O and lse
+    torch.cuda.synchronize()
+    rows = [(f"fwd  nt, dropout p={args.attn_pdrop}      ", fwd_drop),
+            ("bwd  nt, D in-kernel, + bias, dropout", lambda: bwd_drop(dbias))]
+    for name, fn in rows:
+        print(f"{name} {timeit(fn)*1e3:8.1f} us")
