@@ -318,6 +318,46 @@ int ob_gemm_bf16_route(int transA, int transB, int64_t M, int64_t N, int64_t K,
                        float beta, int aligned16, int env_mask,
                        const char* force, int32_t* out);
 
+/* ---- hipBLASLt solution choice -----------------------
+ * A library GEMM shape is 13 int64s: {transA, transB, M, N, K, lda, ldb, ldc,
+ * fp32 out, beta != 0, bias epilogue, C-input is a buffer other than C,
+ * fp32 A/B}, row-major semantics as in ob_gemm_lt*.  All host-only, and all
+ * on the layer's driving thread: the per-stream plan caches they read or
+ * rebuild are not locked, so none may run while a step is in flight or
+ * beside a layer call on another thread.
+ *
+ * ob_layer_lt_shapes: the library GEMM shapes of a layer description at
+ * M = max_batch * seq_len, the ones ob_layer_create tunes; writes up to cap
+ * shapes and returns their number (-1 on a null argument).  No GPU call.
+ * ob_gemm_lt_tune: measures the heuristic's first OB_LT_TUNE_N (default 8,
+ * at most 128) candidates for one shape on scratch operands and records the
+ * winner in the process-wide table, unless the table has the shape already.
+ * A no-op with OB_LT_TUNE=0.
+ * ob_gemm_lt_choice: out[10] = {has an entry, chosen solution index, tuned
+ * (0: tuning was abandoned, top-1 runs), top-1's solution index, top-1's
+ * microseconds, the chosen solution's microseconds, candidates tried,
+ * candidates dropped, tuning wall milliseconds, top-1's max - min over the
+ * rounds (the margin a challenger must beat)}; the two kernel names go to
+ * top1_name / chosen_name (name_cap bytes each, may be null).
+ * ob_gemm_lt_candidates: the candidates the tuner timed, fastest first
+ * (solution index, position in the candidate list, median microseconds);
+ * writes up to cap and returns their number (-1 on a null argument).
+ * ob_gemm_lt_table_size: entries in the table.
+ * ob_gemm_lt_untuned_uses: library GEMM calls so far, with tuning on, whose
+ * shape had no table entry when its plan was built (0 for a training step
+ * at the batch the layers were created for).
+ * ob_gemm_lt_plan_index: the solution index of the plan this stream holds
+ * for a shape, -1 if it has none. */
+int ob_layer_lt_shapes(const ob_layer_desc* desc, int64_t* out, int cap);
+int ob_gemm_lt_tune(const int64_t* shape);
+int ob_gemm_lt_choice(const int64_t* shape, double* out, char* top1_name,
+                      char* chosen_name, int name_cap);
+int ob_gemm_lt_candidates(const int64_t* shape, int32_t* index, int32_t* pos,
+                          double* us, int cap);
+int64_t ob_gemm_lt_table_size(void);
+int64_t ob_gemm_lt_untuned_uses(void);
+int ob_gemm_lt_plan_index(const int64_t* shape, void* stream);
+
 /* Fused causal flash attention on packed bf16 qkv [B, Sq, 3H] (head_dim 64,
  * Sq % 128 == 0) without transposed operand copies: the kernels read the
  * column-major MFMA operands from their row-major LDS tiles.

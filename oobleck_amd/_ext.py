@@ -140,6 +140,22 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.ob_gemm_bf16_route.argtypes = [i32, i32, i64, i64, i64, i64, i64, i32,
                                        i32, f32, i32, i32, ctypes.c_char_p,
                                        ctypes.POINTER(ctypes.c_int32)]
+    lib.ob_gemm_lt_bias_res.argtypes = [i32, i32, i64, i64, i64, f32, vp, i64,
+                                        vp, i64, vp, i64, i32, vp, vp, vp]
+    # hipBLASLt solution choice; a shape is LT_SHAPE_FIELDS int64s
+    shape = ctypes.POINTER(i64)
+    lib.ob_layer_lt_shapes.argtypes = [ctypes.POINTER(ObLayerDesc), shape, i32]
+    lib.ob_gemm_lt_tune.argtypes = [shape]
+    lib.ob_gemm_lt_choice.argtypes = [shape, ctypes.POINTER(ctypes.c_double),
+                                      ctypes.c_char_p, ctypes.c_char_p, i32]
+    lib.ob_gemm_lt_candidates.argtypes = [shape, ctypes.POINTER(i32),
+                                          ctypes.POINTER(i32),
+                                          ctypes.POINTER(ctypes.c_double), i32]
+    lib.ob_gemm_lt_table_size.argtypes = []
+    lib.ob_gemm_lt_table_size.restype = i64
+    lib.ob_gemm_lt_untuned_uses.argtypes = []
+    lib.ob_gemm_lt_untuned_uses.restype = i64
+    lib.ob_gemm_lt_plan_index.argtypes = [shape, vp]
     lib.ob_profile_enable.argtypes = [i32]
     lib.ob_profile_enable.restype = None
     lib.ob_profile_reset.argtypes = []
@@ -190,6 +206,57 @@ def get_ext(build_if_missing: bool = True) -> ctypes.CDLL:
                 "The hot path has no fallback — run __graft_entry__.build().")
     _LIB = _configure(ctypes.CDLL(str(SO_PATH)))
     return _LIB
+
+
+LT_SHAPE_FIELDS = 13
+LT_SHAPE_NAMES = ("tA", "tB", "M", "N", "K", "lda", "ldb", "ldc", "c_f32",
+                  "beta1", "bias", "cin", "ab_f32")
+
+
+def lt_shape(tA, tB, M, N, K, lda, ldb, ldc, c_f32=0, beta1=0, bias=0, cin=0,
+             ab_f32=0):
+    """One library GEMM shape as the int64 array the ob_gemm_lt_* queries
+    take (include/oobleck_stage.h)."""
+    return (ctypes.c_int64 * LT_SHAPE_FIELDS)(tA, tB, M, N, K, lda, ldb, ldc,
+                                              c_f32, beta1, bias, cin, ab_f32)
+
+
+def layer_lt_shapes(desc: ObLayerDesc) -> list[tuple]:
+    """The library GEMM shapes ob_layer_create tunes for a description."""
+    lib = get_ext()
+    n = lib.ob_layer_lt_shapes(ctypes.byref(desc), None, 0)
+    if n < 0:
+        raise RuntimeError("ob_layer_lt_shapes failed")
+    buf = (ctypes.c_int64 * (LT_SHAPE_FIELDS * max(n, 1)))()
+    lib.ob_layer_lt_shapes(ctypes.byref(desc), buf, n)
+    return [tuple(buf[i * LT_SHAPE_FIELDS:(i + 1) * LT_SHAPE_FIELDS])
+            for i in range(n)]
+
+
+def lt_choice(shape) -> dict | None:
+    """The choice table's entry for a shape, or None."""
+    out = (ctypes.c_double * 10)()
+    top1 = ctypes.create_string_buffer(512)
+    chosen = ctypes.create_string_buffer(512)
+    check(get_ext().ob_gemm_lt_choice(lt_shape(*shape), out, top1, chosen, 512),
+          "gemm_lt_choice")
+    if not out[0]:
+        return None
+    return {"index": int(out[1]), "tuned": bool(out[2]),
+            "top1_index": int(out[3]), "us_top1": out[4], "us_chosen": out[5],
+            "tried": int(out[6]), "dropped": int(out[7]), "wall_ms": out[8],
+            "spread_top1": out[9],
+            "top1_kernel": top1.value.decode(),
+            "chosen_kernel": chosen.value.decode()}
+
+
+def lt_candidates(shape, cap: int = 128) -> list[dict]:
+    """The candidates the tuner timed for a shape, fastest first."""
+    idx, pos = (ctypes.c_int32 * cap)(), (ctypes.c_int32 * cap)()
+    us = (ctypes.c_double * cap)()
+    n = get_ext().ob_gemm_lt_candidates(lt_shape(*shape), idx, pos, us, cap)
+    return [{"index": idx[i], "pos": pos[i], "us": us[i]}
+            for i in range(max(0, min(n, cap)))]
 
 
 def check(rc: int, what: str = "") -> None:

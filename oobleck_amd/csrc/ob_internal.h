@@ -223,6 +223,50 @@ extern "C" int ob_gemm_lt_f32(int tA, int tB, int64_t M, int64_t N,
                               float beta, void* C, int64_t ldc,
                               void* stream);
 // ---------------------------------------------------------------------------
+// One library GEMM problem, row-major semantics: everything hipBLASLt's
+// descriptor and layouts are built from, and so the key of both the
+// per-stream plan cache and the process-wide choice table (ob_blaslt.hip).
+// ob_lt_shape_of is the ONE place a key is filled: lt_matmul calls it with
+// the arguments of the call, the layer's shape list (ob_layer_lt_list,
+// ob_layer.hip) through the same two constructors the call sites use.
+struct ob_lt_shape {
+  int tA = 0, tB = 0;
+  int64_t M = 0, N = 0, K = 0, lda = 0, ldb = 0, ldc = 0;
+  int c_f32 = 0;   // fp32 output (else bf16)
+  int beta1 = 0;   // beta != 0
+  int bias = 0;    // fp32 [N] BIAS epilogue
+  int cin = 0;     // the C-input operand is a buffer other than C
+  int ab_f32 = 0;  // fp32 A/B (the reference-dtype leg)
+};
+#define OB_LT_SHAPE_FIELDS 13  // int64s per shape in ob_layer_lt_shapes
+inline ob_lt_shape ob_lt_shape_of(int tA, int tB, int64_t M, int64_t N,
+                                  int64_t K, int64_t lda, int64_t ldb,
+                                  int64_t ldc, int c_f32, float beta,
+                                  bool bias, bool cin, int ab_f32) {
+  ob_lt_shape s;
+  s.tA = tA != 0, s.tB = tB != 0, s.M = M, s.N = N, s.K = K;
+  s.lda = lda, s.ldb = ldb, s.ldc = ldc, s.c_f32 = c_f32 != 0;
+  s.beta1 = beta != 0.f, s.bias = bias, s.cin = cin, s.ab_f32 = ab_f32 != 0;
+  return s;
+}
+// the layer's two library GEMM forms.  linear: out[M,N] = in[M,K] W[N,K]^T
+// (+ bias) (+ res), bf16; dw: gout[actw,dyw] += act[BS,actw]^T dY[BS,dyw],
+// fp32, act rows lda apart.
+inline ob_lt_shape ob_lt_linear(int64_t M, int64_t K, int64_t N, bool bias,
+                                bool res) {
+  return ob_lt_shape_of(0, 1, M, N, K, K, K, N, 0, res ? 1.f : 0.f, bias, res,
+                        0);
+}
+inline ob_lt_shape ob_lt_dw(int64_t actw, int64_t dyw, int64_t BS,
+                            int64_t lda) {
+  return ob_lt_shape_of(1, 0, actw, dyw, BS, lda, dyw, dyw, 1, 1.f, false,
+                        false, 0);
+}
+// tunes one shape if the choice table has no entry for it (host code, never
+// inside a step; a no-op with OB_LT_TUNE=0).  0, or 1 with ob_fail set.
+int ob_lt_tune_shape(const ob_lt_shape& s);
+
+// ---------------------------------------------------------------------------
 // bf16 GEMM call (ob_gemm_bf16.hip): C = alpha * op(A) op(B) (+ bias)
 // (+ residual) (+ beta * C) over an n1 x n2 batch.  Leading dims and batch
 // strides are in elements.  The defaults are the layer's unbatched NT linear

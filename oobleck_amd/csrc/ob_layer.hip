@@ -10,11 +10,13 @@
 //
 // The activation stash is slot-indexed so several microbatches can be in
 // flight, matching deepspeed-style pipe buffers (pipeline.py:556-562).
+#include "ob_gemm_route.h"
 #include "ob_internal.h"
 #include "ob_philox.h"
 
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -293,6 +295,11 @@ extern "C" int64_t ob_layer_param_count(const ob_layer_desc* d) {
   return -1;
 }
 
+static void ob_layer_lt_list(const ob_layer_desc* d, bool resid_drop,
+                             std::vector<ob_lt_shape>* out);
+// vocab rows of the lm_head shadows, logits and their GEMMs
+static int64_t v_pad_of(int64_t V) { return (V + 255) / 256 * 256; }
+
 static int layer_create(const ob_layer_desc* d, const ob_dropout_desc* drop,
                         ob_layer_t* out) {
   if (!d || !out) return ob_fail("create: null arg");
@@ -377,7 +384,7 @@ static int layer_create(const ob_layer_desc* d, const ob_dropout_desc* drop,
   // the glds path AND the 256^2 8-phase kernel (gpt2's 50257 at 128
   // padding lands on 50304 % 256 != 0); shadow pad rows stay zero so
   // padded logits/grads are exactly zero
-  l->v_pad = (V + 255) / 256 * 256;
+  l->v_pad = v_pad_of(V);
   if (d->dtype == 1) {
     int64_t o2 = 0;
     if (d->kind == OB_KIND_BLOCK) {
@@ -441,6 +448,15 @@ static int layer_create(const ob_layer_desc* d, const ob_dropout_desc* drop,
   if (l->p_resid > 0.f) {
     if (ws_ensure(&g_ws.dm1, &g_ws.sz_dm1, BSH)) return 1;
     if (ws_ensure(&g_ws.dm2, &g_ws.sz_dm2, BSH)) return 1;
+  }
+  // pick the library GEMMs' solutions by measurement, once per shape and
+  // process (ob_blaslt.hip; a no-op with OB_LT_TUNE=0)
+  static const bool no_lt = ob_env_flag("OB_NO_BLASLT", false);
+  if (!no_lt) {
+    std::vector<ob_lt_shape> shapes;
+    ob_layer_lt_list(d, l->p_resid > 0.f, &shapes);
+    for (const ob_lt_shape& s : shapes)
+      if (ob_lt_tune_shape(s)) return 1;
   }
   *out = l;
   return 0;
@@ -710,15 +726,105 @@ static int final_forward(ob_layer* l, int slot, const float* in, float* out,
 // GEMM stages its operands with k contiguous (see ob_gemm_bf16.hip).
 // ---------------------------------------------------------------------------
 
+// ---------------------------------------------------------------------------
+// The layer's unbatched GEMMs, the SOLE list of them: the forward and
+// backward below take every such call's dimensions from here, and
+// ob_layer_lt_list hands the same shapes to the hipBLASLt tuner at create
+// time, so the tuned keys and the keys the step uses cannot drift apart.
+enum {
+  LG_QKV = 0, LG_AP, LG_FC, LG_MP,              // forward, bias (+ residual)
+  LG_DX_MP, LG_DX_FC, LG_DX_AP, LG_DX_QKV,      // activation grads
+  LG_DW_MP, LG_DW_FC, LG_DW_AP, LG_DW_QKV,      // weight grads, TN beta=1
+  LG_BLOCK_N
+};
+enum { LG_LM = 0, LG_DLNOUT, LG_DW_LM, LG_FINAL_N };
+
+// res: the two projections fold their residual (false under residual dropout)
+static void block_gemms(int64_t H, int64_t BS, bool res, ob_lt_shape* g) {
+  g[LG_QKV] = ob_lt_linear(BS, H, 3 * H, true, false);
+  g[LG_AP] = ob_lt_linear(BS, H, H, true, res);
+  g[LG_FC] = ob_lt_linear(BS, H, 4 * H, true, false);
+  g[LG_MP] = ob_lt_linear(BS, 4 * H, H, true, res);
+  g[LG_DX_MP] = ob_lt_linear(BS, H, 4 * H, false, false);
+  g[LG_DX_FC] = ob_lt_linear(BS, 4 * H, H, false, false);
+  g[LG_DX_AP] = ob_lt_linear(BS, H, H, false, false);
+  g[LG_DX_QKV] = ob_lt_linear(BS, 3 * H, H, false, false);
+  g[LG_DW_MP] = ob_lt_dw(4 * H, H, BS, 4 * H);
+  g[LG_DW_FC] = ob_lt_dw(H, 4 * H, BS, H);
+  g[LG_DW_AP] = ob_lt_dw(H, H, BS, H);
+  g[LG_DW_QKV] = ob_lt_dw(H, 3 * H, BS, H);
+}
+
+// lm_head N = v_pad, d_lnout K = v_pad, dW_lm M = V over v_pad-wide rows
+static void final_gemms(int64_t H, int64_t V, int64_t v_pad, int64_t BS,
+                        ob_lt_shape* g) {
+  g[LG_LM] = ob_lt_linear(BS, H, v_pad, false, false);
+  g[LG_DLNOUT] = ob_lt_linear(BS, v_pad, H, false, false);
+  g[LG_DW_LM] = ob_lt_dw(V, H, BS, v_pad);
+}
+
+// does the step offer this shape to hipBLASLt?  A linear goes by the bf16
+// route rule; a weight grad always does.
+static bool lt_routed(const ob_lt_shape& s) {
+  if (s.tA) return true;
+  const ob_gemm_env env = {false, false, false, nullptr};
+  return ob_gemm_bf16_pick(0, 1, s.M, s.N, s.K, 1, 1, BF_OUT_BF16, 1, 0.f,
+                           true, env)
+      .try_lt_first;
+}
+
+// host-only: the library GEMM shapes of a layer at M = max_batch * seq_len.
+// resid_drop adds the projections' residual-free form (training forwards
+// under residual dropout) beside the folded one (eval forwards).
+static void ob_layer_lt_list(const ob_layer_desc* d, bool resid_drop,
+                             std::vector<ob_lt_shape>* out) {
+  if (d->dtype != 1) return;
+  const int64_t H = d->n_embd, V = d->vocab_size;
+  const int64_t BS = (int64_t)d->max_batch * d->seq_len;
+  ob_lt_shape g[LG_BLOCK_N];
+  int n = 0;
+  if (d->kind == OB_KIND_BLOCK) {
+    block_gemms(H, BS, true, g);
+    n = LG_BLOCK_N;
+  } else if (d->kind == OB_KIND_FINAL) {
+    final_gemms(H, V, v_pad_of(V), BS, g);
+    n = LG_FINAL_N;
+  }
+  for (int i = 0; i < n; i++)
+    if (lt_routed(g[i])) out->push_back(g[i]);
+  if (d->kind == OB_KIND_BLOCK && resid_drop) {
+    block_gemms(H, BS, false, g);
+    for (int i : {LG_AP, LG_MP})
+      if (lt_routed(g[i])) out->push_back(g[i]);
+  }
+}
+
+extern "C" int ob_layer_lt_shapes(const ob_layer_desc* d, int64_t* out,
+                                  int cap) {
+  if (!d || (!out && cap > 0)) return -1;
+  std::vector<ob_lt_shape> v;
+  ob_layer_lt_list(d, false, &v);
+  for (int i = 0; i < (int)v.size() && i < cap; i++) {
+    const ob_lt_shape& s = v[i];
+    int64_t* o = out + (int64_t)i * OB_LT_SHAPE_FIELDS;
+    o[0] = s.tA, o[1] = s.tB, o[2] = s.M, o[3] = s.N, o[4] = s.K;
+    o[5] = s.lda, o[6] = s.ldb, o[7] = s.ldc, o[8] = s.c_f32, o[9] = s.beta1;
+    o[10] = s.bias, o[11] = s.cin, o[12] = s.ab_f32;
+  }
+  return (int)v.size();
+}
+
 // unbatched NT linear, bf16 out: out[M,N] = in[M,K] @ W[N,K]^T (+ bias)
 // (+ res).  The forward projections, the dX GEMMs, lm_head and d_lnout.
-static int linear_bf(const void* in, int64_t M, int64_t K, const void* W,
-                     int64_t N, const float* bias, const void* res, void* out,
+static int linear_bf(const ob_lt_shape& s, const void* in, const void* W,
+                     const float* bias, const void* res, void* out,
                      void* stream) {
+  if ((bias != nullptr) != (s.bias != 0) || (res != nullptr) != (s.cin != 0))
+    return ob_fail("linear_bf: operands do not match the listed shape");
   ob_bf16_gemm g;
   g.A = in, g.B = W, g.C = out, g.bias = bias, g.residual = res;
-  g.M = M, g.N = N, g.K = K, g.lda = K, g.ldb = K, g.ldc = N;
-  g.stream = stream;
+  g.M = s.M, g.N = s.N, g.K = s.K, g.lda = s.lda, g.ldb = s.ldb;
+  g.ldc = s.ldc, g.stream = stream;
   return ob_gemm_bf16_run(g);
 }
 
@@ -736,16 +842,17 @@ static ob_bf16_gemm attn_gemm(int tA, int tB, int64_t M, int64_t N, int64_t K,
 // weight-grad GEMM for bf16: materialize X^T / dY^T (cheap HBM transpose)
 // so the GEMM runs on the fast NT glds path instead of the
 // transpose-staged TN case (~150 TF measured there).
-static int dw_bf16_ws(const __bf16* act, int64_t actw, const __bf16* dY,
-                      int64_t dyw, int64_t BS, float* gout, int64_t ldc,
-                      float* w1, float* w2, void* stream) {
+static int dw_bf16_ws(const ob_lt_shape& s, const __bf16* act,
+                      const __bf16* dY, float* gout, float* w1, float* w2,
+                      void* stream) {
+  const int64_t actw = s.M, dyw = s.N, BS = s.K, ldc = s.ldc;
   // direct TN via hipBLASLt with beta=1 accumulation into the fp32 flat
   // grads: no transpose materialization, no atomics (measured 694 TF on
   // the fc dW shape vs 436 for transpose + atomic NT)
   static const bool no_lt = ob_env_flag("OB_NO_BLASLT", false);
-  if (!no_lt && ldc == dyw) {
-    const int r = ob_gemm_lt(1, 0, actw, dyw, BS, 1.f, act, actw, dY, dyw,
-                             1.f, gout, ldc, 1, stream);
+  if (!no_lt) {
+    const int r = ob_gemm_lt(s.tA, s.tB, s.M, s.N, s.K, 1.f, act, s.lda, dY,
+                             s.ldb, 1.f, gout, s.ldc, s.c_f32, stream);
     if (r >= 0) return r;
   }
   // gout[actw,dyw] += act^T dY, atomically, K = BS split to fill the chip
@@ -776,6 +883,8 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   const BlockParams bp = block_params(H);
   const bool dA = l->slot_drop[slot] && l->p_attn > 0.f;
   const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;
+  ob_lt_shape lg[LG_BLOCK_N];
+  block_gemms(H, BS, !dR, lg);
 
   // ln1 reads the input once and also writes its stash copy x
   __bf16* x = (__bf16*)(st + l->o_x);
@@ -787,7 +896,7 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
     return 1;
   __bf16* qkv = (__bf16*)(st + l->o_qkv);
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
-              linear_bf(ln1, BS, H, sh + l->sh_qkv_t, 3 * H, p + bp.b_qkv,
+              linear_bf(lg[LG_QKV], ln1, sh + l->sh_qkv_t, p + bp.b_qkv,
                         nullptr, qkv, stream)))
     return 1;
   __bf16* am = (__bf16*)(st + l->o_attnm);
@@ -849,7 +958,7 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   }
   __bf16* hmid = (__bf16*)(st + l->o_hmid);
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
-              linear_bf(am, BS, H, sh + l->sh_ap_t, H, p + bp.b_attnproj,
+              linear_bf(lg[LG_AP], am, sh + l->sh_ap_t, p + bp.b_attnproj,
                         dR ? nullptr : x, hmid, stream)))
     return 1;
   // residual dropout: the GEMM wrote the biased projection only
@@ -866,7 +975,7 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
     return 1;
   __bf16* u = (__bf16*)(st + l->o_u);
   if (OB_PROF(OB_PF_FC_FWD, stream,
-              linear_bf(ln2, BS, H, sh + l->sh_fc_t, 4 * H, p + bp.b_fc,
+              linear_bf(lg[LG_FC], ln2, sh + l->sh_fc_t, p + bp.b_fc,
                         nullptr, u, stream)))
     return 1;
   __bf16* gact = (__bf16*)(st + l->o_g);
@@ -874,7 +983,7 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
               ob_gelu_fwd_bf16(u, gact, BS * 4 * H, stream)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
-              linear_bf(gact, BS, 4 * H, sh + l->sh_mp_t, H,
+              linear_bf(lg[LG_MP], gact, sh + l->sh_mp_t,
                         p + bp.b_mlpproj, dR ? nullptr : hmid, out, stream)))
     return 1;
   if (dR &&
@@ -893,6 +1002,8 @@ static int final_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   float* st = l->stash + (int64_t)slot * l->slot_stride;
   const float* p = l->params;
   if (!labels) return ob_fail("final_forward_bf16: labels required");
+  ob_lt_shape lg[LG_FINAL_N];
+  final_gemms(H, V, l->v_pad, BS, lg);
 
   __bf16* x = (__bf16*)(st + l->o_x);
   int64_t* labs = l->ids + (int64_t)slot * (int64_t)l->d.max_batch * Sq;
@@ -907,7 +1018,7 @@ static int final_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   __bf16* logits = (__bf16*)(st + l->o_logits);
   // N = v_pad (zero-padded shadow rows -> padded logits are exactly 0)
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
-              linear_bf(lnf, BS, H, l->shadows + l->sh_lm, l->v_pad, nullptr,
+              linear_bf(lg[LG_LM], lnf, l->shadows + l->sh_lm, nullptr,
                         nullptr, logits, stream)))
     return 1;
   OB_HIP(hipMemsetAsync(out, 0, sizeof(float), S(stream)));
@@ -948,6 +1059,8 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   // the masks this slot's forward drew, regenerated from its tick
   const bool dA = l->slot_drop[slot] && l->p_attn > 0.f;
   const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;
+  ob_lt_shape lg[LG_BLOCK_N];
+  block_gemms(H, BS, !dR, lg);
 
   // The dW family (transposes + atomic GEMMs + the qkv bias colsum) has
   // no consumer inside this call and no effect on the dX chain (the other
@@ -973,11 +1086,11 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     OB_SIDE_FENCE(S(stream), g_side.stream);  // dm2 ready
   }
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              linear_bf(dmlp, BS, H, sh + l->sh_mp, 4 * H, nullptr, nullptr,
+              linear_bf(lg[LG_DX_MP], dmlp, sh + l->sh_mp, nullptr, nullptr,
                         DY4, stream)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DW, side,
-              dw_bf16_ws(gact, 4 * H, dmlp, H, BS, g + bp.w_mlpproj, H,
+              dw_bf16_ws(lg[LG_DW_MP], gact, dmlp, g + bp.w_mlpproj,
                          g_ws.s1, g_ws.s2, side)))
     return 1;
   // gelu backward also sums its output columns into the b_fc grad
@@ -987,11 +1100,11 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     return 1;
   OB_SIDE_FENCE(S(stream), g_side.stream);  // DY4 post-gelu
   if (OB_PROF(OB_PF_GEMM_DW, side,
-              dw_bf16_ws(ln2, H, DY4, 4 * H, BS, g + bp.w_fc, 4 * H, g_ws.s1,
+              dw_bf16_ws(lg[LG_DW_FC], ln2, DY4, g + bp.w_fc, g_ws.s1,
                          g_ws.s2, side)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              linear_bf(DY4, BS, 4 * H, sh + l->sh_fc, H, nullptr, nullptr,
+              linear_bf(lg[LG_DX_FC], DY4, sh + l->sh_fc, nullptr, nullptr,
                         DLN, stream)))
     return 1;
   // ln2 backward takes the residual straight from dout (din = dout + v,
@@ -1017,11 +1130,11 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   }
   OB_SIDE_FENCE(S(stream), g_side.stream);  // din post-ln2-bwd (dm1 ready)
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              linear_bf(dap, BS, H, sh + l->sh_ap, H, nullptr, nullptr, DATT,
+              linear_bf(lg[LG_DX_AP], dap, sh + l->sh_ap, nullptr, nullptr, DATT,
                         stream)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DW, side,
-              dw_bf16_ws(am, H, dap, H, BS, g + bp.w_attnproj, H, g_ws.s1,
+              dw_bf16_ws(lg[LG_DW_AP], am, dap, g + bp.w_attnproj, g_ws.s1,
                          g_ws.s2, side)))
     return 1;
   // din is re-updated by the final ln1 backward: the main stream must
@@ -1120,11 +1233,11 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
               ob_colsum_bf16(DQKV, g + bp.b_qkv, BS, 3 * H, side)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DW, side,
-              dw_bf16_ws(ln1, H, DQKV, 3 * H, BS, g + bp.w_qkv, 3 * H,
+              dw_bf16_ws(lg[LG_DW_QKV], ln1, DQKV, g + bp.w_qkv,
                          g_ws.s1, g_ws.s2, side)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              linear_bf(DQKV, BS, 3 * H, sh + l->sh_qkv, H, nullptr, nullptr,
+              linear_bf(lg[LG_DX_QKV], DQKV, sh + l->sh_qkv, nullptr, nullptr,
                         DLN, stream)))
     return 1;
   // ln1 backward accumulates into din: wait for the side's din readers
@@ -1151,6 +1264,9 @@ static int final_backward_bf16(ob_layer* l, int slot, const float* dout,
   __bf16* logits = (__bf16*)(st + l->o_logits);
   int64_t* labs = l->ids + (int64_t)slot * (int64_t)l->d.max_batch * Sq;
   __bf16* DLN = (__bf16*)g_ws.bsh1;
+  ob_lt_shape lg[LG_FINAL_N];
+  final_gemms(H, V, l->v_pad, BS, lg);
+  const ob_lt_shape& dwlm = lg[LG_DW_LM];
 
   if (OB_PROF(OB_PF_CE, stream,
               ob_ce_bwd_bf16(logits, labs, st + l->o_lse, dout, B, Sq, V,
@@ -1169,8 +1285,9 @@ static int final_backward_bf16(ob_layer* l, int slot, const float* dout,
     int r = -1;
     if (!no_lt)
       r = OB_PROF(OB_PF_GEMM_DW, side,
-                  ob_gemm_lt(1, 0, V, H, BS, 1.f, logits, l->v_pad, lnf, H,
-                             1.f, g + 2 * H, H, 1, side));
+                  ob_gemm_lt(dwlm.tA, dwlm.tB, dwlm.M, dwlm.N, dwlm.K, 1.f,
+                             logits, dwlm.lda, lnf, dwlm.ldb, 1.f, g + 2 * H,
+                             dwlm.ldc, dwlm.c_f32, side));
     if (r > 0) return 1;
     if (r < 0) {
       __bf16* DLT = (__bf16*)g_ws.s1;
@@ -1187,7 +1304,7 @@ static int final_backward_bf16(ob_layer* l, int slot, const float* dout,
   }
   // d_lnout: K = v_pad (padded dlogits cols and shadow^T cols are zero)
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              linear_bf(logits, BS, l->v_pad, l->shadows + l->sh_lm_t, H,
+              linear_bf(lg[LG_DLNOUT], logits, l->shadows + l->sh_lm_t,
                         nullptr, nullptr, DLN, stream)))
     return 1;
   if (OB_PROF(OB_PF_LN, stream,
