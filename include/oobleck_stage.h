@@ -109,9 +109,15 @@ int ob_layer_create_ex(const ob_layer_desc* desc, const ob_dropout_desc* drop,
                        ob_layer_t* out);
 
 /* 1 when the layer's attention runs the fused flash kernels (bf16 BLOCK,
- * head_dim 64, seq_len % 128 == 0, and for attn_pdrop > 0 neither
- * OB_FLASH_DROP=0 nor OB_FLASH_TR=0), 0 otherwise.  Host-only. */
+ * n_embd % n_head == 0, head_dim 64 or 128, seq_len % 128 == 0; at head_dim
+ * 64, for attn_pdrop > 0, neither OB_FLASH_DROP=0 nor OB_FLASH_TR=0; at
+ * head_dim 128 attn_pdrop == 0 and neither OB_FLASH_TR=0 nor
+ * OB_FLASH_HD128=0), 0 otherwise.  Host-only. */
 int ob_layer_uses_flash(ob_layer_t l);
+/* The same decision for a description, before any layer exists: what
+ * ob_layer_create_ex will take for `desc` with this attn_pdrop.  Host-only,
+ * no GPU call. */
+int ob_flash_eligible(const ob_layer_desc* desc, float attn_pdrop);
 
 /* Training mode (default 1).  0 makes dropout inert (eval): forwards run
  * today's dropout-free path and do not advance the tick. */
@@ -358,8 +364,9 @@ int64_t ob_gemm_lt_table_size(void);
 int64_t ob_gemm_lt_untuned_uses(void);
 int ob_gemm_lt_plan_index(const int64_t* shape, void* stream);
 
-/* Fused causal flash attention on packed bf16 qkv [B, Sq, 3H] (head_dim 64,
- * Sq % 128 == 0) without transposed operand copies: the kernels read the
+/* Fused causal flash attention on packed bf16 qkv [B, Sq, 3H] (H % nh == 0,
+ * head_dim 64 or 128 — the entries dispatch on H / nh —, Sq % 128 == 0)
+ * without transposed operand copies: the kernels read the
  * column-major MFMA operands from their row-major LDS tiles.
  * fwd: O bf16 [B, Sq, H], lse fp32 [B*nh, Sq].
  * bwd: D fp32 [B*nh, Sq] = rowsum(dO * O); dqkv bf16 [B, Sq, 3H];
@@ -373,8 +380,8 @@ int ob_flash_bwd_nt_bf16(const void* qkv, const void* dO, const void* lse,
                          int64_t B, int64_t Sq, int64_t H, int64_t nh,
                          float scale, void* stream);
 /* The same backward without a D input: the dq kernel forms D from O and dO
- * (bit-identical to ob_flash_dsum_bf16's), writes it to D_ws (fp32
- * [B*nh, Sq]) and the dkdv kernel, launched after it, reads it there. */
+ * (at head_dim 64 bit-identical to ob_flash_dsum_bf16's), writes it to D_ws
+ * (fp32 [B*nh, Sq]) and the dkdv kernel, launched after it, reads it there. */
 int ob_flash_bwd_nt_d_bf16(const void* qkv, const void* O, const void* dO,
                            const void* lse, void* D_ws, void* dqkv,
                            void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
@@ -384,8 +391,9 @@ int ob_flash_bwd_nt_d_bf16(const void* qkv, const void* O, const void* dO,
  * index into the full [B*nh, Sq, Sq] square as the dropout section above
  * defines it; no mask or P is stored.  The forward's LSE is that of the
  * undropped P and O = (P * factor) V; the backward must be given the
- * forward's key.  Same shape rules as the plain entries; also p in [0,1) and
- * B*nh*Sq*Sq <= 2^34.  p == 0 launches the plain kernels. */
+ * forward's key.  head_dim 64 only; otherwise the shape rules of the plain
+ * entries; also p in [0,1) and B*nh*Sq*Sq <= 2^34.  p == 0 launches the
+ * plain kernels. */
 int ob_flash_fwd_nt_drop_bf16(const void* qkv, void* O, void* lse, int64_t B,
                               int64_t Sq, int64_t H, int64_t nh, float scale,
                               uint64_t seed, int32_t layer_id, uint64_t tick,

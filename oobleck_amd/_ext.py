@@ -55,6 +55,7 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
                                        ctypes.POINTER(vp)]
     lib.ob_layer_set_training.argtypes = [vp, i32]
     lib.ob_layer_uses_flash.argtypes = [vp]
+    lib.ob_flash_eligible.argtypes = [ctypes.POINTER(ObLayerDesc), f32]
     lib.ob_layer_set_dropout_tick.argtypes = [vp, u64]
     # (seed, layer_id, site, tick, p) select the mask of every dropout entry
     key = [u64, i32, i32, u64, f32]

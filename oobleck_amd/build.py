@@ -11,6 +11,7 @@ SOURCES = [PKG_DIR / "csrc" / "ob_kernels.hip",
            PKG_DIR / "csrc" / "ob_kernels_bf16.hip",
            PKG_DIR / "csrc" / "ob_gemm_bf16.hip",
            PKG_DIR / "csrc" / "ob_flash_bf16.hip",
+           PKG_DIR / "csrc" / "ob_flash_hd128_bf16.hip",
            PKG_DIR / "csrc" / "ob_blaslt.hip",
            PKG_DIR / "csrc" / "ob_optim.hip",
            PKG_DIR / "csrc" / "ob_dropout.hip",
@@ -18,6 +19,7 @@ SOURCES = [PKG_DIR / "csrc" / "ob_kernels.hip",
 HEADERS = [PKG_DIR.parent / "include" / "oobleck_stage.h",
            PKG_DIR / "csrc" / "ob_internal.h",
            PKG_DIR / "csrc" / "ob_flash_fold.h",
+           PKG_DIR / "csrc" / "ob_flash_common.h",
            PKG_DIR / "csrc" / "ob_bf16.h",
            PKG_DIR / "csrc" / "ob_gemm_route.h",
            PKG_DIR / "csrc" / "ob_philox.h"]

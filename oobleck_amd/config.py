@@ -41,6 +41,9 @@ GPT2_SMALL = ModelConfig()
 # examples/gpt3.yaml model_args (the yaml's actual dims; BASELINE.json calls
 # this "GPT-3 2.7B", SURVEY.md §5 notes it is 1600x48 ≈ GPT-2 XL 1.56B)
 GPT2_XL = ModelConfig(n_embd=1600, n_head=25, n_layer=48, n_positions=1024)
+# GPT-3 sizes (Brown et al. 2020, table 2.1); both have head_dim 128
+GPT3_1_3B = ModelConfig(n_embd=2048, n_head=16, n_layer=24, n_positions=2048)
+GPT3_6_7B = ModelConfig(n_embd=4096, n_head=32, n_layer=32, n_positions=2048)
 
 
 @dataclass

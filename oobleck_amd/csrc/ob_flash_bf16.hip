@@ -1,5 +1,8 @@
 // ob_flash_bf16.hip — fused causal flash attention, bf16, head_dim = 64
-// (SURVEY.md "hard part (i)").
+// (SURVEY.md "hard part (i)").  The public
+// nt entries live here and dispatch on H / nh: the head_dim 128 kernels are
+// ob_flash_hd128_bf16.hip (item 17), the helpers both files use
+// ob_flash_common.h.
 //
 // Two families of the same three kernels (forward, dK/dV, dQ):
 //   1. production: k_flash_fwd_nt / k_flash_bwd_dkdv_nt / k_flash_bwd_dq_nt
@@ -62,50 +65,14 @@
 // 4 waves because the per-tile barrier makes a block wait for its longest
 // causal diagonal.
 #include "ob_bf16.h"
+#include "ob_flash_common.h"
 #include "ob_internal.h"
 #include "ob_flash_fold.h"
 #include "ob_philox.h"
 
 #include <cmath>
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-
 static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-__device__ __forceinline__ unsigned bf_pk2(float a, float b) {
-  return bf_bits((__bf16)a) | (bf_bits((__bf16)b) << 16);
-}
-
-// pack-and-exchange: acc-held values (rows pattern) -> A-fragment k-runs
-__device__ __forceinline__ bf16x8 bf_dance(const float* pv8) {
-  unsigned x0 = bf_pk2(pv8[0], pv8[1]);
-  unsigned x1 = bf_pk2(pv8[2], pv8[3]);
-  unsigned y0 = bf_pk2(pv8[4], pv8[5]);
-  unsigned y1 = bf_pk2(pv8[6], pv8[7]);
-  {
-    auto r2 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
-    x0 = r2[0];
-    y0 = r2[1];
-  }
-  {
-    auto r2 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
-    x1 = r2[0];
-    y1 = r2[1];
-  }
-  uint4 fr;
-  fr.x = x0;
-  fr.y = x1;
-  fr.z = y0;
-  fr.w = y1;
-  return __builtin_bit_cast(bf16x8, fr);
-}
-
-// tile row of accumulator element r in lane half kh (the C/D layout above)
-__device__ __forceinline__ int acc_row(int r, int kh) {
-  return (r & 3) + 8 * (r >> 2) + 4 * kh;
-}
 
 // ===========================================================================
 // Production: the "nt" flash kernels — no materialized V^T / Q^T / K^T /
@@ -383,11 +350,29 @@ __global__ __launch_bounds__(256, 3) void k_flash_fwd_nt(
   }
 }
 
+// head size of the nt entries: 64 (the kernels of this file) or 128
+// (ob_flash_hd128_bf16.hip); 0 with ob_fail set for anything else
+static int nt_head_dim(const char* who, int64_t H, int64_t nh) {
+  if (nh <= 0 || H % nh) {
+    ob_fail("%s: n_embd must be a multiple of n_head", who);
+    return 0;
+  }
+  const int64_t hd = H / nh;
+  if (hd != 64 && hd != 128) {
+    ob_fail("%s: head_dim must be 64 or 128", who);
+    return 0;
+  }
+  return (int)hd;
+}
+
 extern "C" int ob_flash_fwd_nt_bf16(const void* qkv, void* O, void* lse,
                                     int64_t B, int64_t Sq, int64_t H,
                                     int64_t nh, float scale, void* stream) {
-  if (H / nh != 64) return ob_fail("flash_fwd_nt: head_dim must be 64");
+  const int hd = nt_head_dim("flash_fwd_nt", H, nh);
+  if (!hd) return 1;
   if (Sq % 128) return ob_fail("flash_fwd_nt: S must be a multiple of 128");
+  if (hd == 128)
+    return ob_flash_hd128_fwd(qkv, O, lse, B, Sq, H, nh, scale, stream);
   const int Z = (int)(B * nh);
   k_flash_fwd_nt<false><<<ob_fold_grid(ob_fold_q_nblk((int)Sq), Z), 256, 0,
                           S(stream)>>>((const __bf16*)qkv, (__bf16*)O,
@@ -400,7 +385,9 @@ extern "C" int ob_flash_fwd_nt_bf16(const void* qkv, void* O, void* lse,
 // shape and key checks shared by the two dropout entries
 static int drop_args_ok(const char* who, int64_t B, int64_t Sq, int64_t H,
                         int64_t nh, float p) {
-  if (nh <= 0 || H / nh != 64) return ob_fail("%s: head_dim must be 64", who);
+  // attention dropout exists at head_dim 64 only
+  if (nh <= 0 || H % nh || H / nh != 64)
+    return ob_fail("%s: head_dim must be 64", who);
   if (Sq <= 0 || Sq % 128)
     return ob_fail("%s: S must be a multiple of 128", who);
   if (!ob_drop_p_ok(p)) return ob_fail("%s: p must be in [0,1)", who);
@@ -878,8 +865,12 @@ extern "C" int ob_flash_bwd_nt_bf16(const void* qkv, const void* dO,
                                     void* dqkv, void* dbias_qkv, int64_t B,
                                     int64_t Sq, int64_t H, int64_t nh,
                                     float scale, void* stream) {
-  if (H / nh != 64) return ob_fail("flash_bwd_nt: head_dim must be 64");
+  const int hd = nt_head_dim("flash_bwd_nt", H, nh);
+  if (!hd) return 1;
   if (Sq % 128) return ob_fail("flash_bwd_nt: S must be a multiple of 128");
+  if (hd == 128)
+    return ob_flash_hd128_bwd(qkv, nullptr, dO, lse, const_cast<void*>(D),
+                              dqkv, dbias_qkv, B, Sq, H, nh, scale, stream);
   if (launch_dkdv_nt<false>(qkv, dO, lse, D, dqkv, dbias_qkv, B, Sq, H, nh,
                             scale, ob_drop_key{}, stream))
     return 1;
@@ -902,8 +893,12 @@ extern "C" int ob_flash_bwd_nt_d_bf16(const void* qkv, const void* O,
                                       void* dbias_qkv, int64_t B, int64_t Sq,
                                       int64_t H, int64_t nh, float scale,
                                       void* stream) {
-  if (H / nh != 64) return ob_fail("flash_bwd_nt_d: head_dim must be 64");
+  const int hd = nt_head_dim("flash_bwd_nt_d", H, nh);
+  if (!hd) return 1;
   if (Sq % 128) return ob_fail("flash_bwd_nt_d: S must be a multiple of 128");
+  if (hd == 128)
+    return ob_flash_hd128_bwd(qkv, O, dO, lse, D_ws, dqkv, dbias_qkv, B, Sq,
+                              H, nh, scale, stream);
   const int Z = (int)(B * nh);
   k_flash_bwd_dq_nt<true, false>
       <<<ob_fold_grid(ob_fold_q_nblk((int)Sq), Z), 256, 0, S(stream)>>>(
@@ -1000,7 +995,9 @@ extern "C" int ob_flash_fold_id(int64_t kind, int64_t Sq, int64_t Z,
   return ok ? 1 : 0;
 }
 
-// D[z][q] = sum_d dO[q,d] * O[q,d]: runs before either backward family
+// D[z][q] = sum_d dO[q,d] * O[q,d]: runs before either backward family.
+// HD = 64: the kernel as it always was.  HD = 128: 16 lanes per row.
+template <int HD>
 __global__ __launch_bounds__(256) void k_flash_dsum(
     const __bf16* __restrict__ O, const __bf16* __restrict__ dO,
     float* __restrict__ D, int Sq, int H, int nh) {
@@ -1008,11 +1005,12 @@ __global__ __launch_bounds__(256) void k_flash_dsum(
   // one-lane-per-element version's 2-B loads measured 3x off roofline
   const int z = blockIdx.z;
   const int b = z / nh, h = z % nh;
-  const int row = blockIdx.x * 32 + (threadIdx.x >> 3);
+  constexpr int LPR = HD / 8;  // lanes per row
+  const int row = blockIdx.x * (256 / LPR) + (threadIdx.x / LPR);
   if (row >= Sq) return;
-  const int l8 = threadIdx.x & 7;
+  const int l8 = threadIdx.x & (LPR - 1);
   const int64_t off =
-      (int64_t)b * Sq * H + (int64_t)row * H + h * 64 + l8 * 8;
+      (int64_t)b * Sq * H + (int64_t)row * H + h * HD + l8 * 8;
   const uint4 ov = *reinterpret_cast<const uint4*>(O + off);
   const uint4 dv = *reinterpret_cast<const uint4*>(dO + off);
   float s = 0.f;
@@ -1020,15 +1018,23 @@ __global__ __launch_bounds__(256) void k_flash_dsum(
   for (int j = 0; j < 8; ++j)
     s += bf2f(bf_extract(ov, j)) * bf2f(bf_extract(dv, j));
 #pragma unroll
-  for (int o = 4; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+  for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
   if (l8 == 0) D[(int64_t)z * Sq + row] = s;
 }
 
 extern "C" int ob_flash_dsum_bf16(const void* O, const void* dO, void* D,
                                   int64_t B, int64_t Sq, int64_t H, int64_t nh,
                                   void* stream) {
+  if (nh > 0 && H == 128 * nh) {
+    dim3 grid((unsigned)((Sq + 15) / 16), 1, (unsigned)(B * nh));
+    k_flash_dsum<128><<<grid, 256, 0, S(stream)>>>(
+        (const __bf16*)O, (const __bf16*)dO, (float*)D, (int)Sq, (int)H,
+        (int)nh);
+    OB_LAUNCH_CHECK();
+    return 0;
+  }
   dim3 grid((unsigned)((Sq + 31) / 32), 1, (unsigned)(B * nh));
-  k_flash_dsum<<<grid, 256, 0, S(stream)>>>(
+  k_flash_dsum<64><<<grid, 256, 0, S(stream)>>>(
       (const __bf16*)O, (const __bf16*)dO, (float*)D, (int)Sq, (int)H,
       (int)nh);
   OB_LAUNCH_CHECK();

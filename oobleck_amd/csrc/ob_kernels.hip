@@ -623,8 +623,9 @@ extern "C" int ob_layernorm_fwd_f32(const void* x, const void* w, const void* b,
 // per thread-owned columns, one atomicAdd per column per block.
 // dx_i (+)= rstd*( dy_i*w_i − mean_c(dy*w) − xhat_i * mean_c(dy*w*xhat) )
 #define LN_CHUNK 16
+#define LN_MAX_H (256 * 48)
 
-template <bool DX_ACCUM>
+template <bool DX_ACCUM, int CPT>
 __global__ __launch_bounds__(256) void k_ln_bwd(
     const float* __restrict__ x, const float* __restrict__ w,
     const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -632,11 +633,12 @@ __global__ __launch_bounds__(256) void k_ln_bwd(
     float* __restrict__ dw, float* __restrict__ db, int64_t rows, int H) {
   __shared__ float lds4[4];
   const int64_t r0 = (int64_t)blockIdx.x * LN_CHUNK;
-  // register accumulators for up to 8 columns per thread (H <= 2048 here;
-  // GPT-2 H is 768/1600 — LN is only applied across n_embd).  Fixed-bound
+  // register accumulators for CPT columns per thread, H <= 256 * CPT: 8
+  // for H <= 2048 (GPT-2 H is 768/1600 — LN is only applied across
+  // n_embd), 16/32/48 for the GPT-3 widths up to 12288.  Fixed-bound
   // unrolled loops keep the arrays in registers (hipcc sends runtime-indexed
   // local arrays to scratch).
-  float accw[8] = {0}, accb[8] = {0};
+  float accw[CPT] = {0}, accb[CPT] = {0};
   const int64_t rend = imin64d(rows, r0 + LN_CHUNK);
   for (int64_t row = r0; row < rend; ++row) {
     const float* xr = x + row * H;
@@ -644,7 +646,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd(
     const float mu = mean[row], rs = rstd[row];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < CPT; ++j) {
       const int c = threadIdx.x + j * 256;
       if (c < H) {
         const float xhat = (xr[c] - mu) * rs;
@@ -659,7 +661,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd(
     const float m2 = block_sum256(s2, lds4) / H;
     float* dxr = dx + row * H;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < CPT; ++j) {
       const int c = threadIdx.x + j * 256;
       if (c < H) {
         const float xhat = (xr[c] - mu) * rs;
@@ -673,7 +675,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd(
     __syncthreads();
   }
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
+  for (int j = 0; j < CPT; ++j) {
     const int c = threadIdx.x + j * 256;
     if (c < H) {
       atomicAdd(&dw[c], accw[j]);
@@ -687,18 +689,26 @@ extern "C" int ob_layernorm_bwd_f32(const void* x, const void* w,
                                     const void* dy, void* dx, void* dw,
                                     void* db, int64_t rows, int64_t H,
                                     int dx_accum, void* stream) {
-  if (H > 2048) return ob_fail("ln_bwd: H > 2048 unsupported");
+  if (H > LN_MAX_H) return ob_fail("ln_bwd: H > 12288 unsupported");
   const int grid = (int)((rows + LN_CHUNK - 1) / LN_CHUNK);
-  if (dx_accum)
-    k_ln_bwd<true><<<grid, 256, 0, S(stream)>>>(
-        (const float*)x, (const float*)w, (const float*)mean,
-        (const float*)rstd, (const float*)dy, (float*)dx, (float*)dw,
-        (float*)db, rows, (int)H);
-  else
-    k_ln_bwd<false><<<grid, 256, 0, S(stream)>>>(
-        (const float*)x, (const float*)w, (const float*)mean,
-        (const float*)rstd, (const float*)dy, (float*)dx, (float*)dw,
-        (float*)db, rows, (int)H);
+#define OB_LNF(A_, C_)                                                 \
+  k_ln_bwd<A_, C_><<<grid, 256, 0, S(stream)>>>(                       \
+      (const float*)x, (const float*)w, (const float*)mean,            \
+      (const float*)rstd, (const float*)dy, (float*)dx, (float*)dw,    \
+      (float*)db, rows, (int)H)
+  // the smallest columns-per-thread count that covers H
+  if (dx_accum) {
+    if (H <= 2048) OB_LNF(true, 8);
+    else if (H <= 4096) OB_LNF(true, 16);
+    else if (H <= 8192) OB_LNF(true, 32);
+    else OB_LNF(true, 48);
+  } else {
+    if (H <= 2048) OB_LNF(false, 8);
+    else if (H <= 4096) OB_LNF(false, 16);
+    else if (H <= 8192) OB_LNF(false, 32);
+    else OB_LNF(false, 48);
+  }
+#undef OB_LNF
   OB_LAUNCH_CHECK();
   return 0;
 }

@@ -304,7 +304,12 @@ extern "C" int ob_layernorm_fwd_bf16(const void* x, const void* w,
 }
 
 #define BLN_CHUNK 16
-template <bool DX_ACCUM>
+// CPT = columns per thread: the block covers H <= 256 * CPT columns.  8 is
+// the kernel as it always was (H <= 2048); 16, 32 and 48 carry wider rows
+// (to 12288) with the same fixed-bound loops, so the accumulators stay in
+// registers.
+#define BLN_MAX_H (256 * 48)
+template <bool DX_ACCUM, int CPT>
 __global__ __launch_bounds__(256) void k_ln_bwd_bf16(
     const __bf16* __restrict__ x, const float* __restrict__ w,
     const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -312,7 +317,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd_bf16(
     float* __restrict__ dw, float* __restrict__ db, int64_t rows, int H) {
   __shared__ float lds4[4];
   const int64_t r0 = (int64_t)blockIdx.x * BLN_CHUNK;
-  float accw[8] = {0}, accb[8] = {0};
+  float accw[CPT] = {0}, accb[CPT] = {0};
   const int64_t rend = bmin64(rows, r0 + BLN_CHUNK);
   for (int64_t row = r0; row < rend; ++row) {
     const __bf16* xr = x + row * H;
@@ -320,7 +325,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd_bf16(
     const float mu = mean[row], rs = rstd[row];
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < CPT; ++j) {
       const int c = threadIdx.x + j * 256;
       if (c < H) {
         const float xhat = (bf2f(xr[c]) - mu) * rs;
@@ -336,7 +341,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd_bf16(
     const float m2 = bblock_sum256(s2, lds4) / H;
     __bf16* dxr = dx + row * H;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < CPT; ++j) {
       const int c = threadIdx.x + j * 256;
       if (c < H) {
         const float xhat = (bf2f(xr[c]) - mu) * rs;
@@ -347,7 +352,7 @@ __global__ __launch_bounds__(256) void k_ln_bwd_bf16(
     __syncthreads();
   }
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
+  for (int j = 0; j < CPT; ++j) {
     const int c = threadIdx.x + j * 256;
     if (c < H) {
       atomicAdd(&dw[c], accw[j]);
@@ -361,23 +366,31 @@ extern "C" int ob_layernorm_bwd_bf16(const void* x, const void* w,
                                      const void* dy, void* dx, void* dw,
                                      void* db, int64_t rows, int64_t H,
                                      int dx_accum, void* stream) {
-  if (H > 2048) return ob_fail("ln_bwd_bf16: H > 2048 unsupported");
+  if (H > BLN_MAX_H) return ob_fail("ln_bwd_bf16: H > 12288 unsupported");
   if (H % 8) return ob_fail("ln_bwd_bf16: H must be a multiple of 8");
   if (H >= 512 && H <= 1024)
     return ob_layernorm_bwd_res_bf16(x, w, mean, rstd, dy,
                                      dx_accum ? dx : nullptr, dx, dw, db,
                                      nullptr, nullptr, rows, H, stream);
   const int grid = (int)((rows + BLN_CHUNK - 1) / BLN_CHUNK);
-  if (dx_accum)
-    k_ln_bwd_bf16<true><<<grid, 256, 0, S(stream)>>>(
-        (const __bf16*)x, (const float*)w, (const float*)mean,
-        (const float*)rstd, (const __bf16*)dy, (__bf16*)dx, (float*)dw,
-        (float*)db, rows, (int)H);
-  else
-    k_ln_bwd_bf16<false><<<grid, 256, 0, S(stream)>>>(
-        (const __bf16*)x, (const float*)w, (const float*)mean,
-        (const float*)rstd, (const __bf16*)dy, (__bf16*)dx, (float*)dw,
-        (float*)db, rows, (int)H);
+#define OB_LNB(A_, C_)                                                   \
+  k_ln_bwd_bf16<A_, C_><<<grid, 256, 0, S(stream)>>>(                    \
+      (const __bf16*)x, (const float*)w, (const float*)mean,             \
+      (const float*)rstd, (const __bf16*)dy, (__bf16*)dx, (float*)dw,    \
+      (float*)db, rows, (int)H)
+  // the smallest columns-per-thread count that covers H
+  if (dx_accum) {
+    if (H <= 2048) OB_LNB(true, 8);
+    else if (H <= 4096) OB_LNB(true, 16);
+    else if (H <= 8192) OB_LNB(true, 32);
+    else OB_LNB(true, 48);
+  } else {
+    if (H <= 2048) OB_LNB(false, 8);
+    else if (H <= 4096) OB_LNB(false, 16);
+    else if (H <= 8192) OB_LNB(false, 32);
+    else OB_LNB(false, 48);
+  }
+#undef OB_LNB
   OB_LAUNCH_CHECK();
   return 0;
 }
@@ -595,7 +608,7 @@ extern "C" int ob_layernorm_bwd_res_bf16(const void* x, const void* w,
                                          void* sum_res, void* sum_dx,
                                          int64_t rows, int64_t H,
                                          void* stream) {
-  if (H > 2048) return ob_fail("ln_bwd_bf16: H > 2048 unsupported");
+  if (H > BLN_MAX_H) return ob_fail("ln_bwd_bf16: H > 12288 unsupported");
   if (H % 8) return ob_fail("ln_bwd_bf16: H must be a multiple of 8");
   if (sum_res && !res) return ob_fail("ln_bwd_res_bf16: sum_res needs res");
   if (rows <= 0) return 0;

@@ -207,7 +207,7 @@ struct ob_layer {
   int64_t sh_qkv = 0, sh_qkv_t = 0, sh_ap = 0, sh_ap_t = 0, sh_fc = 0,
           sh_fc_t = 0, sh_mp = 0, sh_mp_t = 0, sh_lm = 0, sh_lm_t = 0;
   int64_t shadow_count = 0;
-  // fused flash-attention path (bf16, head_dim 64, S % 128 == 0): the
+  // fused flash-attention path (bf16, head_dim 64 or 128, S % 128 == 0): the
   // o_p slot holds only the per-row LSE ([Bm*nh, S] floats) instead of
   // the materialized [Bm*nh, S, S] P.
   bool flash = false;
@@ -249,16 +249,36 @@ static bool flash_drop() {
   return on;
 }
 
-// flash applies when head_dim == 64 and S % 128 == 0 (GPT-2 small and
-// XL both qualify); OB_BF16_FLASH=0 falls back to the materialized-P
-// path.  Decided at create time: it sizes the stash.
+// Fused attention at head_dim 128 (ob_flash_hd128_bf16.hip).
+// OB_FLASH_HD128=0 (read once) keeps such a layer on the materialized-P
+// path, as before those kernels existed.
+static bool flash_hd128() {
+  static const bool on = ob_env_flag("OB_FLASH_HD128", true);
+  return on;
+}
+
+// flash applies to bf16 layers with n_embd % n_head == 0, head_dim 64 (GPT-2
+// small and XL) or 128 (the GPT-3 sizes from 1.3B up) and S % 128 == 0;
+// OB_BF16_FLASH=0 falls back to the materialized-P path.  head_dim 128 has
+// production kernels only: no OB_FLASH_TR=0 twins and no dropout variant.
+// Decided at create time: it sizes the stash.
 static bool flash_eligible(const ob_layer_desc* d, float attn_pdrop = 0.f) {
   // only the production kernels have a dropout variant, not the
   // OB_FLASH_TR=0 twins
   if (attn_pdrop > 0.f && !(flash_tr() && flash_drop())) return false;
   static const bool on = ob_env_flag("OB_BF16_FLASH", true);
-  return on && d->dtype == 1 && d->n_embd / d->n_head == 64 &&
-         d->seq_len % 128 == 0;
+  if (!on || d->dtype != 1 || d->n_head <= 0 || d->n_embd % d->n_head ||
+      d->seq_len <= 0 || d->seq_len % 128)
+    return false;
+  const int64_t hd = d->n_embd / d->n_head;
+  if (hd == 128) return attn_pdrop == 0.f && flash_tr() && flash_hd128();
+  return hd == 64;
+}
+
+// the decision ob_layer_create_ex takes for `d` with this attn_pdrop; host
+// only, no GPU call
+extern "C" int ob_flash_eligible(const ob_layer_desc* d, float attn_pdrop) {
+  return d && flash_eligible(d, attn_pdrop) ? 1 : 0;
 }
 
 // parameter offsets (canonical layout, oracle/gpt2_oracle.py::layer_param_spec)

@@ -8,6 +8,12 @@
 # --attn-pdrop P (0 < P < 1) adds the attention-dropout entries
 # (ob_flash_fwd_nt_drop_bf16 / ob_flash_bwd_nt_d_drop_bf16) next to the plain
 # ones.
+#
+# --head-dim 128 times the head_dim 128 kernels behind the same `_nt` entries
+# instead (there are no transposed-operand twins at 128), at --shape B,nh,S,
+# and prints TF next to the microseconds: causal FLOPs, 2*B*nh*S*S*hd for
+# the forward (2 GEMMs over half the square) and 5*B*nh*S*S*hd for the
+# backward (5 GEMMs).  The default, --head-dim 64, prints what it always did.
 import argparse
 import ctypes
 import pathlib
@@ -21,9 +27,12 @@ from oobleck_amd._ext import check, get_ext  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--attn-pdrop", type=float, default=0.0, metavar="P",
                 help="also time the dropout variants of the three kernels")
+ap.add_argument("--head-dim", type=int, default=64, choices=(64, 128))
+ap.add_argument("--shape", default="8,12,1024", metavar="B,nh,S")
 args = ap.parse_args()
 
-B, nh, S, hd = 8, 12, 1024, 64
+B, nh, S = (int(v) for v in args.shape.split(","))
+hd = args.head_dim
 H = nh * hd
 DEV = "cuda"
 
@@ -141,6 +150,23 @@ def bwd_drop(bias=None):
         B, S, H, nh, scale, DROP_KEY[0], DROP_KEY[1], DROP_KEY[2],
         args.attn_pdrop, stream()))
 
+
+if hd == 128:
+    fwd_new()
+    dsum()
+    torch.cuda.synchronize()
+    unit = B * nh * S * S * hd * 1e-12  # TFLOP per causal GEMM pair / 2
+    print(f"head_dim 128, (B, nh, S) = ({B}, {nh}, {S})")
+    rows = [("fwd  nt                      ", fwd_new, 2),
+            ("bwd  nt (dq + dkdv)          ", bwd_new, 5),
+            ("bwd  nt + bias in-kernel     ", lambda: bwd_new(dbias), 5),
+            ("dsum alone                   ", dsum, 0),
+            ("bwd  nt, D in-kernel, + bias ", lambda: bwd_new_d(dbias), 5)]
+    for name, fn, gemms in rows:
+        us = timeit(fn) * 1e3
+        tf = f" {gemms * unit / (us * 1e-6):7.1f} TF" if gemms else ""
+        print(f"{name} {us:8.1f} us{tf}")
+    sys.exit(0)
 
 O_old = torch.empty_like(O)
 fwd_old()
