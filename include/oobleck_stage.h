@@ -418,6 +418,83 @@ int64_t ob_flash_fold_grid(int64_t kind, int64_t Sq, int64_t Z);
 int ob_flash_fold_id(int64_t kind, int64_t Sq, int64_t Z, int64_t id,
                      int64_t* z, int64_t* block);
 
+/* ---- deterministic mode -------------------------------
+ * Off by default; with it off every launch is what it was.  With it on, every
+ * array a bf16 training step produces (loss, activations, din, flat grads,
+ * params and AdamW moments) is bit-identical between two fresh processes of
+ * the same build on the same machine, given the same inputs, seeds, batch,
+ * slot sequence and stream usage.  Shown: layer stacks
+ * of all three kinds on every attention / LayerNorm / dropout route, and the
+ * GPT-2 small benchmark step with forward and backward on ONE stream.  NOT
+ * covered: a forward that runs beside a backward on another stream (the
+ * Python pipeline's pp1 overlap, which it therefore leaves off in the mode),
+ * and OB_NO_BLASLT=1.  The sums that otherwise go through
+ * atomicAdd (bias grads, LayerNorm dw/db, embedding grads, the loss) are
+ * formed in a fixed order instead: each block stores its per-column partial
+ * to its own row of a slab and ob_colpart_finish_f32 folds the rows; the
+ * embedding backward is owner-computes.  In the mode the b_qkv grad of a
+ * flash layer is the column sum of the bf16-ROUNDED dqkv (ob_colsum_det_bf16
+ * on the side stream; the flash kernels get dbias_qkv = NULL), the
+ * hand-written dW fallback runs with split-K 1 and the library GEMMs run
+ * their top-1 solution (no tuning, as with OB_LT_TUNE=0).
+ *
+ * The switch is process-wide.  Its default is the environment's
+ * OB_DETERMINISTIC=1, read once.  ob_set_deterministic fails once a layer has
+ * been created in the process; creating an fp32 layer (dtype 0) fails while
+ * the mode is on.  ob_deterministic returns the current value. */
+int ob_set_deterministic(int on);
+int ob_deterministic(void);
+
+/* The _det entries: their atomic siblings with the column sums run-to-run
+ * bit-stable.  ws is a caller-owned fp32 device slab of ob_det_ws_count(which,
+ * M, N) floats (rows, H for LayerNorm; B*Sq, 1 for the loss), written before
+ * it is read in every call and not shared with a call on another stream.
+ * Everything else (dx, du, dm, lse) is bit-identical to the sibling's. */
+enum {
+  OB_DET_WS_COLSUM = 0,
+  OB_DET_WS_GELU = 1,
+  OB_DET_WS_LN = 2,
+  OB_DET_WS_DROP_CS = 3,
+  OB_DET_WS_CE = 4
+};
+int64_t ob_det_ws_count(int which, int64_t M, int64_t N); /* host-only */
+int ob_colsum_det_bf16(const void* X, void* db, int64_t M, int64_t N,
+                       void* ws, void* stream);
+int ob_gelu_bwd_colsum_det_bf16(const void* u, const void* dg, void* du,
+                                void* db, int64_t M, int64_t N, void* ws,
+                                void* stream);
+int ob_layernorm_bwd_res_det_bf16(const void* x, const void* w,
+                                  const void* mean, const void* rstd,
+                                  const void* dy, const void* res, void* dx,
+                                  void* dw, void* db, void* sum_res,
+                                  void* sum_dx, int64_t rows, int64_t H,
+                                  void* ws, void* stream);
+int ob_dropout_scale_colsum_det_bf16(uint64_t seed, int32_t layer_id,
+                                     int32_t site, uint64_t tick, float p,
+                                     const void* dy, void* dm, void* db,
+                                     int64_t M, int64_t N, void* ws,
+                                     void* stream);
+int ob_ce_fwd_det_bf16(const void* logits, const void* labels, void* lse,
+                       void* loss, int64_t B, int64_t Sq, int64_t V,
+                       int64_t ld, void* ws, void* stream);
+/* dwte[ids[r]] += dout[r], dwpe[r % Sq] += dout[r] over bf16 dout [B,Sq,H],
+ * owner-computes: each position and each distinct id has one block, which
+ * adds its rows in ascending row order and does one += per element.  The
+ * _drop form scales by the keep mask of (seed, layer_id, site, tick, p). */
+int ob_embed_bwd_det_bf16(const void* ids, const void* dout, void* dwte,
+                          void* dwpe, int64_t B, int64_t Sq, int64_t H,
+                          void* stream);
+int ob_embed_bwd_drop_det_bf16(uint64_t seed, int32_t layer_id, int32_t site,
+                               uint64_t tick, float p, const void* ids,
+                               const void* dout, void* dwte, void* dwpe,
+                               int64_t B, int64_t Sq, int64_t H, void* stream);
+/* dst[c] += fold(part[0..nblk)[c]) for c < N over a slab with row stride ld.
+ * The association depends on nblk only: group g (0..7) adds rows g, g + 8,
+ * ... in ascending order, the group sums are then added in ascending g, and
+ * the total is added to dst[c]. */
+int ob_colpart_finish_f32(const void* part, int64_t nblk, int64_t N,
+                          int64_t ld, void* dst, void* stream);
+
 /* dtype casts (weight shadows / activation conversion). */
 int ob_f32_to_bf16(const void* x, void* y, int64_t n, void* stream);
 int ob_f32_to_bf16_t(const void* x, void* y, int64_t rows, int64_t cols,

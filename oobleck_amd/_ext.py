@@ -178,6 +178,25 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.ob_flash_bwd_nt_d_drop_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp,
                                                 i64, i64, i64, i64, f32, u64,
                                                 i32, u64, f32, vp]
+    # deterministic mode (include/oobleck_stage.h)
+    lib.ob_set_deterministic.argtypes = [i32]
+    lib.ob_deterministic.argtypes = []
+    lib.ob_det_ws_count.argtypes = [i32, i64, i64]
+    lib.ob_det_ws_count.restype = i64
+    lib.ob_colsum_det_bf16.argtypes = [vp, vp, i64, i64, vp, vp]
+    lib.ob_gelu_bwd_colsum_det_bf16.argtypes = [vp, vp, vp, vp, i64, i64, vp,
+                                                vp]
+    lib.ob_layernorm_bwd_res_det_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp,
+                                                  vp, vp, vp, vp, i64, i64,
+                                                  vp, vp]
+    lib.ob_dropout_scale_colsum_det_bf16.argtypes = key + [vp, vp, vp, i64,
+                                                           i64, vp, vp]
+    lib.ob_ce_fwd_det_bf16.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64,
+                                       vp, vp]
+    lib.ob_embed_bwd_det_bf16.argtypes = [vp, vp, vp, vp, i64, i64, i64, vp]
+    lib.ob_embed_bwd_drop_det_bf16.argtypes = key + [vp, vp, vp, vp, i64,
+                                                     i64, i64, vp]
+    lib.ob_colpart_finish_f32.argtypes = [vp, i64, i64, i64, vp, vp]
     p64 = ctypes.POINTER(ctypes.c_int64)
     lib.ob_flash_fold_rows.argtypes = [i64, i64, i64, i64, p64, p64, p64]
     lib.ob_flash_fold_grid.argtypes = [i64, i64, i64]
@@ -258,6 +277,21 @@ def lt_candidates(shape, cap: int = 128) -> list[dict]:
     n = get_ext().ob_gemm_lt_candidates(lt_shape(*shape), idx, pos, us, cap)
     return [{"index": idx[i], "pos": pos[i], "us": us[i]}
             for i in range(max(0, min(n, cap)))]
+
+
+# which-codes of ob_det_ws_count (OB_DET_WS_* of include/oobleck_stage.h)
+DET_WS_COLSUM, DET_WS_GELU, DET_WS_LN, DET_WS_DROP_CS, DET_WS_CE = range(5)
+
+
+def set_deterministic(on: bool) -> None:
+    """Turn the process-wide deterministic mode on or off (default: the
+    environment's OB_DETERMINISTIC=1).  Raises once a layer has been created
+    in this process."""
+    check(get_ext().ob_set_deterministic(1 if on else 0), "set_deterministic")
+
+
+def deterministic() -> bool:
+    return bool(get_ext().ob_deterministic())
 
 
 def check(rc: int, what: str = "") -> None:

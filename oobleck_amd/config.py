@@ -63,6 +63,9 @@ class TrainingConfig:
     # dropout masks are a pure function of (dropout_seed, pipeline id, layer,
     # site, optimizer step, microbatch, element): no RNG state to carry
     dropout_seed: int = 0
+    # deterministic mode: bit-reproducible bf16 steps.
+    # Process-wide; the pipeline applies it before it creates its first layer.
+    deterministic: bool = False
 
     @property
     def num_microbatches(self) -> int:

@@ -103,7 +103,9 @@ std::atomic<int64_t> g_untuned_uses{0};
 
 bool lt_tune_on() {
   static const bool on = ob_env_flag("OB_LT_TUNE", true);
-  return on;
+  // deterministic mode: the tuned choice is a per-process measurement, so
+  // every plan is the heuristic's top-1, as with OB_LT_TUNE=0
+  return on && !ob_deterministic();
 }
 
 LtCtx* lt_ctx(void* stream) {
@@ -201,7 +203,7 @@ LtPlan lt_plan_build(LtCtx* ctx, const Key& key, const void* bias) {
     auto it = g_tab.find(key);
     if (it == g_tab.end())
       p.untuned = lt_tune_on();
-    else if (it->second.tuned)
+    else if (it->second.tuned && lt_tune_on())
       index = it->second.index;
   }
   if (index >= 0 && lt_algo_from_index(ctx->h, p.p, key.s, index, &p.algo)) {

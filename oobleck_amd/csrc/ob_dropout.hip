@@ -185,8 +185,10 @@ static int launch_ew_bf16(const ob_drop_key& key, const void* x,
 
 // any dtype / width / alignment.  Block = 256 columns x DCS_ROWS rows, one
 // atomic per column per block; the colsum adds the values as stored (the
-// bf16-rounded dm on the bf16 path).
-template <typename T>
+// bf16-rounded dm on the bf16 path).  DET (deterministic mode, both kernels):
+// db is the partial slab [gridDim.y][N]; row blockIdx.y = rows [128 y,
+// 128 y + 128), a function of the shape alone; every (y, c < N) is written.
+template <typename T, bool DET = false>
 __global__ __launch_bounds__(256) void k_drop_cs(ob_drop_key key, const T* dy,
                                                  T* dm,
                                                  float* __restrict__ db,
@@ -205,13 +207,15 @@ __global__ __launch_bounds__(256) void k_drop_cs(ob_drop_key key, const T* dy,
     dst(dm + e, v);
     acc += dld(dm + e);
   }
-  atomicAdd(&db[c], acc);
+  if constexpr (DET) db[(int64_t)blockIdx.y * N + c] = acc;
+  else atomicAdd(&db[c], acc);
 }
 
 // bf16, N % 8 == 0, 16-byte aligned: the k_gelu_bwd_cs_bf16 tiling.  Block =
 // 16 col-threads x 16 row-threads over 128 cols x DCS_ROWS rows; a thread
 // owns 8 fixed columns and keeps 4 rows in flight.  Column partials fold
 // registers -> wave shfl -> LDS -> one atomic per column per block.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void k_drop_cs_bf16(
     ob_drop_key key, const __bf16* dy, __bf16* dm, float* __restrict__ db,
     int64_t M, int64_t N) {
@@ -263,19 +267,21 @@ __global__ __launch_bounds__(256) void k_drop_cs_bf16(
   __syncthreads();
   if (tid < 128) {
     const int64_t c = (int64_t)blockIdx.x * 128 + tid;
-    if (c < N)
-      atomicAdd(&db[c],
-                red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]);
+    if (c < N) {
+      const float t = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+      if constexpr (DET) db[(int64_t)blockIdx.y * N + c] = t;
+      else atomicAdd(&db[c], t);
+    }
   }
 }
 
-template <typename T>
+template <typename T, bool DET = false>
 static int launch_cs(const ob_drop_key& key, const void* dy, void* dm,
                      void* db, int64_t M, int64_t N, void* stream) {
   dim3 grid((unsigned)((N + 255) / 256),
             (unsigned)((M + DCS_ROWS - 1) / DCS_ROWS));
-  k_drop_cs<T><<<grid, 256, 0, S(stream)>>>(key, (const T*)dy, (T*)dm,
-                                            (float*)db, M, N);
+  k_drop_cs<T, DET><<<grid, 256, 0, S(stream)>>>(key, (const T*)dy, (T*)dm,
+                                                 (float*)db, M, N);
   OB_LAUNCH_CHECK();
   return 0;
 }
@@ -329,6 +335,105 @@ __global__ __launch_bounds__(256) void k_embed_bwd_drop(
   }
 }
 
+// Deterministic embedding backward, owner-computes (no atomics, no slab):
+// blocks [0, BS) are token rows, blocks [BS, BS + Sq) positions.
+// dwpe[s]: its block adds the B rows of position s in ascending b and does
+// one += per column.  dwte: the block of token row t is the LEADER of its id
+// if no row < t has the same id; a leader adds the rows with that id in
+// ascending row order and does one += per column; other blocks leave.  Every
+// dwte / dwpe element has one writer per launch.  The ids are scanned once
+// per block, 256 rows at a time: the four waves' ballots of "same id" go to
+// LDS and every thread walks their set bits in ascending order for the
+// EBD_CPT columns it holds in registers (wider rows take further passes).
+// DROP applies the keep*scale of k_embed_bwd_drop (a dropped element is
+// skipped).
+#define EBD_CPT 8
+template <bool DROP>
+__global__ __launch_bounds__(256) void k_embed_bwd_det_bf16(
+    ob_drop_key key, const int64_t* __restrict__ ids,
+    const __bf16* __restrict__ dout, float* __restrict__ dwte,
+    float* __restrict__ dwpe, int64_t BS, int Sq, int H) {
+  __shared__ int dup;
+  __shared__ unsigned long long match[4];
+  auto term = [&](int64_t row, int c, float* acc) {
+    const float d = dld(dout + row * H + c);
+    if (DROP) {
+      if (drop_word_at(key, row * H + c) >= key.thr)
+        *acc += __fmul_rn(d, key.scale);
+    } else {
+      *acc += d;
+    }
+  };
+  if ((int64_t)blockIdx.x >= BS) {
+    const int64_t s = (int64_t)blockIdx.x - BS;
+    for (int c = threadIdx.x; c < H; c += 256) {
+      float acc = 0.f;
+      for (int64_t row = s; row < BS; row += Sq) term(row, c, &acc);
+      dwpe[s * H + c] += acc;
+    }
+    return;
+  }
+  const int64_t t = blockIdx.x;
+  const int64_t id = ids[t];
+  if (threadIdx.x == 0) dup = 0;
+  __syncthreads();
+  int mine = 0;
+  for (int64_t r = threadIdx.x; r < t; r += 256) mine |= ids[r] == id;
+  if (mine) dup = 1;  // every writer stores the same value
+  __syncthreads();
+  if (dup) return;  // block-uniform
+  const int wid = threadIdx.x >> 6;
+  for (int cb = 0; cb < H; cb += 256 * EBD_CPT) {
+    float acc[EBD_CPT] = {0};
+    for (int64_t base = t; base < BS; base += 256) {
+      const int64_t r = base + threadIdx.x;
+      const unsigned long long m = __ballot(r < BS && ids[r] == id);
+      if ((threadIdx.x & 63) == 0) match[wid] = m;
+      __syncthreads();
+#pragma unroll 1
+      for (int w = 0; w < 4; ++w) {
+        unsigned long long bits = match[w];
+        while (bits) {
+          const int i = __ffsll((long long)bits) - 1;
+          bits &= bits - 1;
+          const int64_t row = base + w * 64 + i;
+#pragma unroll
+          for (int j = 0; j < EBD_CPT; ++j) {
+            const int c = cb + threadIdx.x + j * 256;
+            if (c < H) term(row, c, &acc[j]);
+          }
+        }
+      }
+      __syncthreads();  // match[] is rewritten by the next chunk
+    }
+#pragma unroll
+    for (int j = 0; j < EBD_CPT; ++j) {
+      const int c = cb + threadIdx.x + j * 256;
+      if (c < H) dwte[id * H + c] += acc[j];
+    }
+  }
+}
+
+// key null: no dropout
+int ob_embed_bwd_det(const ob_drop_key* key, const int64_t* ids,
+                     const void* dout, float* dwte, float* dwpe, int64_t B,
+                     int64_t Sq, int64_t H, void* stream) {
+  const int64_t BS = B * Sq;
+  if (BS <= 0 || H <= 0) return 0;
+  if (BS * H > OB_DROP_MAX_N) return ob_fail("dropout: n > 2^34 unsupported");
+  if (BS + Sq > INT32_MAX) return ob_fail("embed_bwd_det: B*S too large");
+  const unsigned grid = (unsigned)(BS + Sq);
+  if (key)
+    k_embed_bwd_det_bf16<true><<<grid, 256, 0, S(stream)>>>(
+        *key, ids, (const __bf16*)dout, dwte, dwpe, BS, (int)Sq, (int)H);
+  else
+    k_embed_bwd_det_bf16<false><<<grid, 256, 0, S(stream)>>>(
+        ob_drop_key{}, ids, (const __bf16*)dout, dwte, dwpe, BS, (int)Sq,
+        (int)H);
+  OB_LAUNCH_CHECK();
+  return 0;
+}
+
 int ob_embed_fwd_drop(const ob_drop_key& key, int bf16, const int64_t* ids,
                       const float* wte, const float* wpe, void* out, int64_t B,
                       int64_t Sq, int64_t H, void* stream) {
@@ -379,19 +484,33 @@ int ob_drop_add(const ob_drop_key& key, int bf16, const void* t,
 
 int ob_drop_scale_colsum(const ob_drop_key& key, int bf16, const void* dy,
                          void* dm, void* db, int64_t M, int64_t N,
-                         void* stream) {
+                         void* stream, float* ws) {
   if (M <= 0 || N <= 0) return 0;
   if (M * N > OB_DROP_MAX_N) return ob_fail("dropout: n > 2^34 unsupported");
+  if (ws && !bf16)
+    return ob_fail("dropout_scale_colsum: the slab form is bf16 only");
   if (!bf16) return launch_cs<float>(key, dy, dm, db, M, N, stream);
+  // ws (deterministic mode): the kernels' db is the slab, folded afterwards
+  const int64_t nblk = (M + DCS_ROWS - 1) / DCS_ROWS;
   if (N % 8 == 0 && al16(dy) && al16(dm)) {
-    dim3 grid((unsigned)((N + 127) / 128),
-              (unsigned)((M + DCS_ROWS - 1) / DCS_ROWS));
-    k_drop_cs_bf16<<<grid, 256, 0, S(stream)>>>(
-        key, (const __bf16*)dy, (__bf16*)dm, (float*)db, M, N);
+    dim3 grid((unsigned)((N + 127) / 128), (unsigned)nblk);
+    if (ws)
+      k_drop_cs_bf16<true><<<grid, 256, 0, S(stream)>>>(
+          key, (const __bf16*)dy, (__bf16*)dm, ws, M, N);
+    else
+      k_drop_cs_bf16<false><<<grid, 256, 0, S(stream)>>>(
+          key, (const __bf16*)dy, (__bf16*)dm, (float*)db, M, N);
     OB_LAUNCH_CHECK();
-    return 0;
+  } else if (ws ? launch_cs<__bf16, true>(key, dy, dm, ws, M, N, stream)
+                : launch_cs<__bf16, false>(key, dy, dm, db, M, N, stream)) {
+    return 1;
   }
-  return launch_cs<__bf16>(key, dy, dm, db, M, N, stream);
+  return ws ? ob_colpart_finish_f32(ws, nblk, N, N, db, stream) : 0;
+}
+
+// slab floats of ob_drop_scale_colsum with ws: one row per DCS_ROWS rows
+int64_t ob_drop_cs_ws_count(int64_t M, int64_t N) {
+  return (M + DCS_ROWS - 1) / DCS_ROWS * N;
 }
 
 // ---------------------------------------------------------------------------
@@ -468,4 +587,28 @@ extern "C" int ob_dropout_scale_colsum_bf16(uint64_t seed, int32_t layer_id,
                                             void* stream) {
   OB_DROP_KEY();
   return ob_drop_scale_colsum(key, 1, dy, dm, db, M, N, stream);
+}
+extern "C" int ob_dropout_scale_colsum_det_bf16(
+    uint64_t seed, int32_t layer_id, int32_t site, uint64_t tick, float p,
+    const void* dy, void* dm, void* db, int64_t M, int64_t N, void* ws,
+    void* stream) {
+  OB_DROP_KEY();
+  if (!ws) return ob_fail("dropout_scale_colsum_det_bf16: ws required");
+  return ob_drop_scale_colsum(key, 1, dy, dm, db, M, N, stream, (float*)ws);
+}
+extern "C" int ob_embed_bwd_det_bf16(const void* ids, const void* dout,
+                                     void* dwte, void* dwpe, int64_t B,
+                                     int64_t Sq, int64_t H, void* stream) {
+  return ob_embed_bwd_det(nullptr, (const int64_t*)ids, dout, (float*)dwte,
+                          (float*)dwpe, B, Sq, H, stream);
+}
+extern "C" int ob_embed_bwd_drop_det_bf16(uint64_t seed, int32_t layer_id,
+                                          int32_t site, uint64_t tick, float p,
+                                          const void* ids, const void* dout,
+                                          void* dwte, void* dwpe, int64_t B,
+                                          int64_t Sq, int64_t H,
+                                          void* stream) {
+  OB_DROP_KEY();
+  return ob_embed_bwd_det(&key, (const int64_t*)ids, dout, (float*)dwte,
+                          (float*)dwpe, B, Sq, H, stream);
 }

@@ -115,15 +115,24 @@ int ob_drop_scale(const ob_drop_key& key, int bf16, const void* x, void* y,
                   int64_t n, void* stream);
 int ob_drop_add(const ob_drop_key& key, int bf16, const void* t,
                 const void* res, void* y, int64_t n, void* stream);
+// ws non-null (bf16 only): the column sums go through that slab of
+// ob_drop_cs_ws_count floats (deterministic mode)
 int ob_drop_scale_colsum(const ob_drop_key& key, int bf16, const void* dy,
                          void* dm, void* db, int64_t M, int64_t N,
-                         void* stream);
+                         void* stream, float* ws = nullptr);
 int ob_embed_fwd_drop(const ob_drop_key& key, int bf16, const int64_t* ids,
                       const float* wte, const float* wpe, void* out, int64_t B,
                       int64_t Sq, int64_t H, void* stream);
 int ob_embed_bwd_drop(const ob_drop_key& key, int bf16, const int64_t* ids,
                       const void* dout, float* dwte, float* dwpe, int64_t B,
                       int64_t Sq, int64_t H, void* stream);
+// deterministic mode (bf16 only): the colsum through a slab of
+// ob_drop_cs_ws_count floats; the owner-computes embedding backward (key
+// null: no dropout)
+int64_t ob_drop_cs_ws_count(int64_t M, int64_t N);
+int ob_embed_bwd_det(const ob_drop_key* key, const int64_t* ids,
+                     const void* dout, float* dwte, float* dwpe, int64_t B,
+                     int64_t Sq, int64_t H, void* stream);
 
 // bf16-path launchers (defined in ob_kernels_bf16.hip; the flash family
 // and ob_transpose_bf16_b in ob_flash_bf16.hip; the GEMMs, below, in
@@ -200,6 +209,26 @@ int ob_flash_bwd_nt_d_bf16(const void* qkv, const void* O, const void* dO,
                            void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
                            int64_t nh, float scale, void* stream);
 }
+// The reductions' common form (ob_kernels_bf16.hip): ws null runs the
+// atomic kernels, as the entries above do; ws non-null (deterministic mode)
+// runs the DET kernels through that slab of ob_det_ws_count floats, as the
+// public _det entries do.  The layer passes its mode's slab or null.
+int ob_layernorm_bwd_ws(const void* x, const void* w, const void* mean,
+                        const void* rstd, const void* dy, void* dx, void* dw,
+                        void* db, int64_t rows, int64_t H, int dx_accum,
+                        float* ws, void* stream);
+int ob_layernorm_bwd_res_ws(const void* x, const void* w, const void* mean,
+                            const void* rstd, const void* dy, const void* res,
+                            void* dx, void* dw, void* db, void* sum_res,
+                            void* sum_dx, int64_t rows, int64_t H, float* ws,
+                            void* stream);
+int ob_colsum_ws(const void* X, void* db, int64_t M, int64_t N, float* ws,
+                 void* stream);
+int ob_gelu_bwd_colsum_ws(const void* u, const void* dg, void* du, void* db,
+                          int64_t M, int64_t N, float* ws, void* stream);
+int ob_ce_fwd_ws(const void* logits, const void* labels, void* lse,
+                 void* loss, int64_t B, int64_t Sq, int64_t V, int64_t ld,
+                 float* ws, void* stream);
 // hipBLASLt path for plain GEMMs (ob_blaslt.hip); returns -1 when the
 // heuristic offers no algo (caller falls back to the hand-written path)
 extern "C" int ob_gemm_lt(int tA, int tB, int64_t M, int64_t N, int64_t K,

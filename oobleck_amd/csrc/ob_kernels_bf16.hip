@@ -309,7 +309,11 @@ extern "C" int ob_layernorm_fwd_bf16(const void* x, const void* w,
 // (to 12288) with the same fixed-bound loops, so the accumulators stay in
 // registers.
 #define BLN_MAX_H (256 * 48)
-template <bool DX_ACCUM, int CPT>
+// DET (deterministic mode): dw / db are this launch's
+// partial slabs [gridDim.x][H]; the block stores its column sums to row
+// blockIdx.x and ob_colpart_finish folds the rows in a fixed order.  Block b
+// owns rows [16 b, 16 b + 16): a function of the shape alone.
+template <bool DX_ACCUM, int CPT, bool DET = false>
 __global__ __launch_bounds__(256) void k_ln_bwd_bf16(
     const __bf16* __restrict__ x, const float* __restrict__ w,
     const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -355,10 +359,64 @@ __global__ __launch_bounds__(256) void k_ln_bwd_bf16(
   for (int j = 0; j < CPT; ++j) {
     const int c = threadIdx.x + j * 256;
     if (c < H) {
-      atomicAdd(&dw[c], accw[j]);
-      atomicAdd(&db[c], accb[j]);
+      if constexpr (DET) {
+        dw[(int64_t)blockIdx.x * H + c] = accw[j];
+        db[(int64_t)blockIdx.x * H + c] = accb[j];
+      } else {
+        atomicAdd(&dw[c], accw[j]);
+        atomicAdd(&db[c], accb[j]);
+      }
     }
   }
+}
+
+static int colpart_finish(const float* part, int64_t nblk, int64_t N,
+                          int64_t ld, int64_t vstride, float* d0, float* d1,
+                          float* d2, float* d3, void* stream);
+
+// ws null: dw / db are added atomically; else (deterministic mode) through
+// the slab ws, ob_det_ws_count(OB_DET_WS_LN, rows, H) floats
+int ob_layernorm_bwd_ws(const void* x, const void* w, const void* mean,
+                       const void* rstd, const void* dy, void* dx, void* dw,
+                       void* db, int64_t rows, int64_t H, int dx_accum,
+                       float* ws, void* stream) {
+  if (H > BLN_MAX_H) return ob_fail("ln_bwd_bf16: H > 12288 unsupported");
+  if (H % 8) return ob_fail("ln_bwd_bf16: H must be a multiple of 8");
+  if (H >= 512 && H <= 1024)
+    return ob_layernorm_bwd_res_ws(x, w, mean, rstd, dy, dx_accum ? dx : nullptr, dx,
+                           dw, db, nullptr, nullptr, rows, H, ws, stream);
+  if (ws && rows <= 0) return 0;
+  const int grid = (int)((rows + BLN_CHUNK - 1) / BLN_CHUNK);
+  // deterministic: the kernel's dw / db are the two slabs [grid][H]
+  float* const pw = ws ? ws : (float*)dw;
+  float* const pb = ws ? ws + (int64_t)grid * H : (float*)db;
+#define OB_LNB(A_, C_, D_)                                               \
+  k_ln_bwd_bf16<A_, C_, D_><<<grid, 256, 0, S(stream)>>>(                \
+      (const __bf16*)x, (const float*)w, (const float*)mean,             \
+      (const float*)rstd, (const __bf16*)dy, (__bf16*)dx, pw, pb, rows,  \
+      (int)H)
+  // the smallest columns-per-thread count that covers H
+#define OB_LNB_H(A_, D_)                       \
+  do {                                         \
+    if (H <= 2048) OB_LNB(A_, 8, D_);          \
+    else if (H <= 4096) OB_LNB(A_, 16, D_);    \
+    else if (H <= 8192) OB_LNB(A_, 32, D_);    \
+    else OB_LNB(A_, 48, D_);                   \
+  } while (0)
+  if (ws) {
+    if (dx_accum) OB_LNB_H(true, true);
+    else OB_LNB_H(false, true);
+  } else {
+    if (dx_accum) OB_LNB_H(true, false);
+    else OB_LNB_H(false, false);
+  }
+#undef OB_LNB_H
+#undef OB_LNB
+  OB_LAUNCH_CHECK();
+  if (ws)
+    return colpart_finish(ws, grid, H, H, (int64_t)grid * H, (float*)dw,
+                          (float*)db, nullptr, nullptr, stream);
+  return 0;
 }
 
 extern "C" int ob_layernorm_bwd_bf16(const void* x, const void* w,
@@ -366,33 +424,8 @@ extern "C" int ob_layernorm_bwd_bf16(const void* x, const void* w,
                                      const void* dy, void* dx, void* dw,
                                      void* db, int64_t rows, int64_t H,
                                      int dx_accum, void* stream) {
-  if (H > BLN_MAX_H) return ob_fail("ln_bwd_bf16: H > 12288 unsupported");
-  if (H % 8) return ob_fail("ln_bwd_bf16: H must be a multiple of 8");
-  if (H >= 512 && H <= 1024)
-    return ob_layernorm_bwd_res_bf16(x, w, mean, rstd, dy,
-                                     dx_accum ? dx : nullptr, dx, dw, db,
-                                     nullptr, nullptr, rows, H, stream);
-  const int grid = (int)((rows + BLN_CHUNK - 1) / BLN_CHUNK);
-#define OB_LNB(A_, C_)                                                   \
-  k_ln_bwd_bf16<A_, C_><<<grid, 256, 0, S(stream)>>>(                    \
-      (const __bf16*)x, (const float*)w, (const float*)mean,             \
-      (const float*)rstd, (const __bf16*)dy, (__bf16*)dx, (float*)dw,    \
-      (float*)db, rows, (int)H)
-  // the smallest columns-per-thread count that covers H
-  if (dx_accum) {
-    if (H <= 2048) OB_LNB(true, 8);
-    else if (H <= 4096) OB_LNB(true, 16);
-    else if (H <= 8192) OB_LNB(true, 32);
-    else OB_LNB(true, 48);
-  } else {
-    if (H <= 2048) OB_LNB(false, 8);
-    else if (H <= 4096) OB_LNB(false, 16);
-    else if (H <= 8192) OB_LNB(false, 32);
-    else OB_LNB(false, 48);
-  }
-#undef OB_LNB
-  OB_LAUNCH_CHECK();
-  return 0;
+  return ob_layernorm_bwd_ws(x, w, mean, rstd, dy, dx, dw, db, rows, H, dx_accum,
+                     nullptr, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -417,7 +450,11 @@ extern "C" int ob_layernorm_bwd_bf16(const void* x, const void* w,
 #define BLNR_ROWS (BLNR_WAVES * BLNR_WROWS)
 #define BLNR_MAXGRID 1024
 
-template <bool HAS_RES, bool SUMS>
+// DET (deterministic mode): o0..o3 are partial slabs [gridDim.x][H]; the
+// block stores its folded columns to row blockIdx.x.  Block b owns the
+// 32-row chunks b, b + gridDim.x, ... and gridDim.x = min(chunks, 1024): a
+// function of the row count alone, and every block has a chunk.
+template <bool HAS_RES, bool SUMS, bool DET = false>
 __global__ __launch_bounds__(64 * BLNR_WAVES) void k_ln_bwd_bf16_rs(
     const __bf16* __restrict__ x, const float* __restrict__ w,
     const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -591,7 +628,11 @@ __global__ __launch_bounds__(64 * BLNR_WAVES) void k_ln_bwd_bf16_rs(
       float t = 0.f;
 #pragma unroll
       for (int k = 0; k < BLNR_WAVES; ++k) t += red[k][c];
-      if (out) atomicAdd(&out[c], t);
+      if constexpr (DET) {
+        if (out) out[(int64_t)blockIdx.x * H + c] = t;
+      } else {
+        if (out) atomicAdd(&out[c], t);
+      }
     }
     __syncthreads();
   }
@@ -601,13 +642,11 @@ __global__ __launch_bounds__(64 * BLNR_WAVES) void k_ln_bwd_bf16_rs(
 // dw/db += as ob_layernorm_bwd_bf16; sum_res += colsum(res) and sum_dx +=
 // colsum(dx) when non-null.  Widths outside the wave path compose the
 // unfused kernels and give the same results.
-extern "C" int ob_layernorm_bwd_res_bf16(const void* x, const void* w,
-                                         const void* mean, const void* rstd,
-                                         const void* dy, const void* res,
-                                         void* dx, void* dw, void* db,
-                                         void* sum_res, void* sum_dx,
-                                         int64_t rows, int64_t H,
-                                         void* stream) {
+int ob_layernorm_bwd_res_ws(const void* x, const void* w, const void* mean,
+                           const void* rstd, const void* dy, const void* res,
+                           void* dx, void* dw, void* db, void* sum_res,
+                           void* sum_dx, int64_t rows, int64_t H, float* ws,
+                           void* stream) {
   if (H > BLN_MAX_H) return ob_fail("ln_bwd_bf16: H > 12288 unsupported");
   if (H % 8) return ob_fail("ln_bwd_bf16: H must be a multiple of 8");
   if (sum_res && !res) return ob_fail("ln_bwd_res_bf16: sum_res needs res");
@@ -616,33 +655,69 @@ extern "C" int ob_layernorm_bwd_res_bf16(const void* x, const void* w,
     const bool sums = sum_res || sum_dx;
     const int64_t nchunks = (rows + BLNR_ROWS - 1) / BLNR_ROWS;
     const int grid = (int)bmin64(nchunks, BLNR_MAXGRID);
-#define OB_LNRS(R_, S_)                                                     \
-  k_ln_bwd_bf16_rs<R_, S_><<<grid, 64 * BLNR_WAVES, 0, S(stream)>>>(        \
+    // deterministic: vector v's slab [grid][H] at ws + v * grid * H (null
+    // outputs stay null)
+    const int64_t vs = (int64_t)grid * H;
+    float* const p0 = ws ? ws : (float*)dw;
+    float* const p1 = ws ? ws + vs : (float*)db;
+    float* const p2 = ws ? (sum_res ? ws + 2 * vs : nullptr) : (float*)sum_res;
+    float* const p3 = ws ? (sum_dx ? ws + 3 * vs : nullptr) : (float*)sum_dx;
+#define OB_LNRS(R_, S_, D_)                                                 \
+  k_ln_bwd_bf16_rs<R_, S_, D_><<<grid, 64 * BLNR_WAVES, 0, S(stream)>>>(    \
       (const __bf16*)x, (const float*)w, (const float*)mean,                \
       (const float*)rstd, (const __bf16*)dy, (const __bf16*)res,            \
-      (__bf16*)dx, (float*)dw, (float*)db, (float*)sum_res, (float*)sum_dx, \
-      rows, (int)H)
-    if (res) {
-      if (sums) OB_LNRS(true, true);
-      else OB_LNRS(true, false);
-    } else {
-      if (sums) OB_LNRS(false, true);
-      else OB_LNRS(false, false);
-    }
+      (__bf16*)dx, p0, p1, p2, p3, rows, (int)H)
+#define OB_LNRS_D(D_)                    \
+  do {                                   \
+    if (res) {                           \
+      if (sums) OB_LNRS(true, true, D_); \
+      else OB_LNRS(true, false, D_);     \
+    } else {                             \
+      if (sums) OB_LNRS(false, true, D_);\
+      else OB_LNRS(false, false, D_);    \
+    }                                    \
+  } while (0)
+    if (ws) OB_LNRS_D(true);
+    else OB_LNRS_D(false);
+#undef OB_LNRS_D
 #undef OB_LNRS
     OB_LAUNCH_CHECK();
+    if (ws)
+      return colpart_finish(ws, grid, H, H, vs, (float*)dw, (float*)db,
+                            (float*)sum_res, (float*)sum_dx, stream);
     return 0;
   }
   // composed path: colsum(res) first (res may alias dx), copy, ln, colsum
-  if (sum_res && ob_colsum_bf16(res, sum_res, rows, H, stream)) return 1;
+  // (deterministic: the three steps are stream-ordered and reuse the slab)
+  if (sum_res && ob_colsum_ws(res, sum_res, rows, H, ws, stream)) return 1;
   if (res && res != dx)
     OB_HIP(hipMemcpyAsync(dx, res, (size_t)(rows * H) * sizeof(__bf16),
                           hipMemcpyDeviceToDevice, S(stream)));
-  if (ob_layernorm_bwd_bf16(x, w, mean, rstd, dy, dx, dw, db, rows, H,
-                            res ? 1 : 0, stream))
+  if (ob_layernorm_bwd_ws(x, w, mean, rstd, dy, dx, dw, db, rows, H, res ? 1 : 0, ws,
+                  stream))
     return 1;
-  if (sum_dx && ob_colsum_bf16(dx, sum_dx, rows, H, stream)) return 1;
+  if (sum_dx && ob_colsum_ws(dx, sum_dx, rows, H, ws, stream)) return 1;
   return 0;
+}
+
+extern "C" int ob_layernorm_bwd_res_bf16(const void* x, const void* w,
+                                         const void* mean, const void* rstd,
+                                         const void* dy, const void* res,
+                                         void* dx, void* dw, void* db,
+                                         void* sum_res, void* sum_dx,
+                                         int64_t rows, int64_t H,
+                                         void* stream) {
+  return ob_layernorm_bwd_res_ws(x, w, mean, rstd, dy, res, dx, dw, db, sum_res,
+                         sum_dx, rows, H, nullptr, stream);
+}
+extern "C" int ob_layernorm_bwd_res_det_bf16(
+    const void* x, const void* w, const void* mean, const void* rstd,
+    const void* dy, const void* res, void* dx, void* dw, void* db,
+    void* sum_res, void* sum_dx, int64_t rows, int64_t H, void* ws,
+    void* stream) {
+  if (!ws) return ob_fail("ln_bwd_res_det_bf16: ws required");
+  return ob_layernorm_bwd_res_ws(x, w, mean, rstd, dy, res, dx, dw, db, sum_res,
+                         sum_dx, rows, H, (float*)ws, stream);
 }
 
 __global__ __launch_bounds__(256) void k_softmax_fwd_bf16(
@@ -852,6 +927,11 @@ extern "C" int ob_gelu_bwd_bf16(const void* u, const void* dg, void* du,
   return 0;
 }
 
+// DET (deterministic mode, both colsum kernels): db is the partial slab
+// [gridDim.y][N]; the block stores its column sums to row blockIdx.y.  Block
+// row y owns rows [T y, T y + T) (T = 256 here, 128 in v9): a function of the
+// shape alone, and every (y, c < N) is written.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void k_colsum_bf16(
     const __bf16* __restrict__ X, float* __restrict__ db, int64_t M,
     int64_t N) {
@@ -861,7 +941,8 @@ __global__ __launch_bounds__(256) void k_colsum_bf16(
   const int64_t r1 = bmin64(M, r0 + 256);
   float acc = 0.f;
   for (int64_t r = r0; r < r1; ++r) acc += bf2f(X[r * N + c]);
-  atomicAdd(&db[c], acc);
+  if constexpr (DET) db[(int64_t)blockIdx.y * N + c] = acc;
+  else atomicAdd(&db[c], acc);
 }
 // vectorized: each thread owns 8 contiguous columns (one uint4 per row)
 __global__ __launch_bounds__(256) void k_colsum_bf16_v8(
@@ -885,7 +966,8 @@ __global__ __launch_bounds__(256) void k_colsum_bf16_v8(
 // a 64-col x 128-row tile; each thread keeps 4 independent uint4 loads
 // in flight (the v8 kernel's single serial load stream measured ~640
 // GB/s); wave shfl + LDS tree reduction, ONE global atomic per column
-// per block.
+// per block (DET: one slab store, see k_colsum_bf16).
+template <bool DET = false>
 __global__ __launch_bounds__(256) void k_colsum_bf16_v9(
     const __bf16* __restrict__ X, float* __restrict__ db, int64_t M,
     int64_t N) {
@@ -931,25 +1013,55 @@ __global__ __launch_bounds__(256) void k_colsum_bf16_v9(
   // first 64 threads: fold 4 waves, one atomic per column
   if (tid < 64) {
     const int64_t c = (int64_t)blockIdx.x * 64 + tid;
-    if (c < N)
-      atomicAdd(&db[c],
-                red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]);
+    if (c < N) {
+      const float t = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+      if constexpr (DET) db[(int64_t)blockIdx.y * N + c] = t;
+      else atomicAdd(&db[c], t);
+    }
   }
+}
+
+// ws null: atomic; else the deterministic form through the slab ws
+// (ob_det_ws_count(OB_DET_WS_COLSUM, M, N) floats)
+int ob_colsum_ws(const void* X, void* db, int64_t M, int64_t N,
+                       float* ws, void* stream) {
+  if (ws && (M <= 0 || N <= 0)) return 0;
+  float* const dst = ws ? ws : (float*)db;
+  int64_t nblk;
+  if (N % 8 == 0) {
+    nblk = (M + 127) / 128;
+    dim3 grid((unsigned)((N + 63) / 64), (unsigned)nblk);
+    if (ws)
+      k_colsum_bf16_v9<true><<<grid, 256, 0, S(stream)>>>((const __bf16*)X,
+                                                          dst, M, N);
+    else
+      k_colsum_bf16_v9<false><<<grid, 256, 0, S(stream)>>>((const __bf16*)X,
+                                                           dst, M, N);
+  } else {
+    nblk = (M + 255) / 256;
+    dim3 grid((unsigned)((N + 255) / 256), (unsigned)nblk);
+    if (ws)
+      k_colsum_bf16<true><<<grid, 256, 0, S(stream)>>>((const __bf16*)X, dst,
+                                                       M, N);
+    else
+      k_colsum_bf16<false><<<grid, 256, 0, S(stream)>>>((const __bf16*)X, dst,
+                                                        M, N);
+  }
+  OB_LAUNCH_CHECK();
+  if (ws)
+    return colpart_finish(ws, nblk, N, N, 0, (float*)db, nullptr, nullptr,
+                          nullptr, stream);
+  return 0;
 }
 
 extern "C" int ob_colsum_bf16(const void* X, void* db, int64_t M, int64_t N,
                               void* stream) {
-  if (N % 8 == 0) {
-    dim3 grid((unsigned)((N + 63) / 64), (unsigned)((M + 127) / 128));
-    k_colsum_bf16_v9<<<grid, 256, 0, S(stream)>>>((const __bf16*)X,
-                                                  (float*)db, M, N);
-  } else {
-    dim3 grid((unsigned)((N + 255) / 256), (unsigned)((M + 255) / 256));
-    k_colsum_bf16<<<grid, 256, 0, S(stream)>>>((const __bf16*)X, (float*)db,
-                                               M, N);
-  }
-  OB_LAUNCH_CHECK();
-  return 0;
+  return ob_colsum_ws(X, db, M, N, nullptr, stream);
+}
+extern "C" int ob_colsum_det_bf16(const void* X, void* db, int64_t M,
+                                  int64_t N, void* ws, void* stream) {
+  if (!ws) return ob_fail("colsum_det_bf16: ws required");
+  return ob_colsum_ws(X, db, M, N, (float*)ws, stream);
 }
 
 // gelu backward fused with the bias grad of the GEMM that produced u:
@@ -975,6 +1087,9 @@ __device__ __forceinline__ float bgelu_grad_fast(float x) {
   return 0.5f * (1.f + t) + 0.5f * x * (1.f - t * t) *
                                 (BGELU_K + 3.f * BGELU_K * BGELU_C * x2);
 }
+// DET (deterministic mode): db is the partial slab [gridDim.y][N], row
+// blockIdx.y = rows [128 y, 128 y + 128), every (y, c < N) written.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void k_gelu_bwd_cs_bf16(
     const __bf16* __restrict__ u, const __bf16* dg, __bf16* du,
     float* __restrict__ db, int64_t M, int64_t N) {
@@ -1026,27 +1141,49 @@ __global__ __launch_bounds__(256) void k_gelu_bwd_cs_bf16(
   __syncthreads();
   if (tid < 128) {
     const int64_t c = (int64_t)blockIdx.x * 128 + tid;
-    if (c < N)
-      atomicAdd(&db[c],
-                red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]);
+    if (c < N) {
+      const float t = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+      if constexpr (DET) db[(int64_t)blockIdx.y * N + c] = t;
+      else atomicAdd(&db[c], t);
+    }
   }
+}
+
+int ob_gelu_bwd_colsum_ws(const void* u, const void* dg, void* du,
+                                void* db, int64_t M, int64_t N, float* ws,
+                                void* stream) {
+  if (M <= 0 || N <= 0) return 0;
+  if (N % 8 == 0) {
+    const int64_t nblk = (M + BGC_ROWS - 1) / BGC_ROWS;
+    dim3 grid((unsigned)((N + 127) / 128), (unsigned)nblk);
+    if (ws)
+      k_gelu_bwd_cs_bf16<true><<<grid, 256, 0, S(stream)>>>(
+          (const __bf16*)u, (const __bf16*)dg, (__bf16*)du, ws, M, N);
+    else
+      k_gelu_bwd_cs_bf16<false><<<grid, 256, 0, S(stream)>>>(
+          (const __bf16*)u, (const __bf16*)dg, (__bf16*)du, (float*)db, M, N);
+    OB_LAUNCH_CHECK();
+    if (ws)
+      return colpart_finish(ws, nblk, N, N, 0, (float*)db, nullptr, nullptr,
+                            nullptr, stream);
+    return 0;
+  }
+  // other widths compose the unfused kernels
+  if (ob_gelu_bwd_bf16(u, dg, du, M * N, stream)) return 1;
+  return ob_colsum_ws(du, db, M, N, ws, stream);
 }
 
 extern "C" int ob_gelu_bwd_colsum_bf16(const void* u, const void* dg,
                                        void* du, void* db, int64_t M,
                                        int64_t N, void* stream) {
-  if (M <= 0 || N <= 0) return 0;
-  if (N % 8 == 0) {
-    dim3 grid((unsigned)((N + 127) / 128),
-              (unsigned)((M + BGC_ROWS - 1) / BGC_ROWS));
-    k_gelu_bwd_cs_bf16<<<grid, 256, 0, S(stream)>>>(
-        (const __bf16*)u, (const __bf16*)dg, (__bf16*)du, (float*)db, M, N);
-    OB_LAUNCH_CHECK();
-    return 0;
-  }
-  // other widths compose the unfused kernels
-  if (ob_gelu_bwd_bf16(u, dg, du, M * N, stream)) return 1;
-  return ob_colsum_bf16(du, db, M, N, stream);
+  return ob_gelu_bwd_colsum_ws(u, dg, du, db, M, N, nullptr, stream);
+}
+extern "C" int ob_gelu_bwd_colsum_det_bf16(const void* u, const void* dg,
+                                           void* du, void* db, int64_t M,
+                                           int64_t N, void* ws,
+                                           void* stream) {
+  if (!ws) return ob_fail("gelu_bwd_colsum_det_bf16: ws required");
+  return ob_gelu_bwd_colsum_ws(u, dg, du, db, M, N, (float*)ws, stream);
 }
 
 __global__ __launch_bounds__(256) void k_embed_fwd_bf16(
@@ -1098,7 +1235,10 @@ extern "C" int ob_embed_bwd_bf16(const void* ids, const void* dout, void* dwte,
 }
 
 // CE with bf16 logits at row stride ld (padded to 8-half alignment); the
-// shift/mean semantics match the fp32 kernels.
+// shift/mean semantics match the fp32 kernels.  DET (deterministic mode):
+// loss is the [BS] slab; every row stores its term (0 for the last position
+// of a sequence) and k_ce_fold adds the slab to the scalar in a fixed order.
+template <bool DET = false>
 __global__ __launch_bounds__(256) void k_ce_fwd_bf16(
     const __bf16* __restrict__ logits, const int64_t* __restrict__ labels,
     float* __restrict__ lse, float* __restrict__ loss, int64_t BS, int Sq,
@@ -1157,20 +1297,157 @@ __global__ __launch_bounds__(256) void k_ce_fwd_bf16(
         const int64_t lab = labels[row + 1];
         const int64_t B = BS / Sq;
         const float inv = 1.f / (float)(B * (Sq - 1));
-        atomicAdd(loss, (l - bf2f(lr[lab])) * inv);
+        const float term = (l - bf2f(lr[lab])) * inv;
+        if constexpr (DET) loss[row] = term;
+        else atomicAdd(loss, term);
+      } else if constexpr (DET) {
+        loss[row] = 0.f;
       }
     }
     __syncthreads();
   }
 }
+// loss += fold(part[0..n)): thread t adds part[t], part[t + 256], ... in
+// ascending order, thread 0 then adds the 256 thread sums in ascending t
+// (threads with no element skipped).  One block: the order depends on n only.
+__global__ __launch_bounds__(256) void k_ce_fold(
+    const float* __restrict__ part, int64_t n, float* __restrict__ loss) {
+  __shared__ float red[256];
+  const int t = threadIdx.x;
+  float s = 0.f;
+  if (t < n) {
+    s = part[t];
+    for (int64_t i = t + 256; i < n; i += 256) s += part[i];
+  }
+  red[t] = s;
+  __syncthreads();
+  if (t == 0) {
+    float a = red[0];
+    const int m = n < 256 ? (int)n : 256;
+    for (int k = 1; k < m; ++k) a += red[k];
+    loss[0] += a;
+  }
+}
+// ws null: the loss is added atomically; else (deterministic mode) through
+// the B * Sq float slab ws
+int ob_ce_fwd_ws(const void* logits, const void* labels, void* lse,
+                 void* loss, int64_t B, int64_t Sq, int64_t V, int64_t ld,
+                 float* ws, void* stream) {
+  if (ws && B * Sq <= 0) return 0;
+  const int grid = (int)bmin64(B * Sq, 16384);
+  if (ws)
+    k_ce_fwd_bf16<true><<<grid, 256, 0, S(stream)>>>(
+        (const __bf16*)logits, (const int64_t*)labels, (float*)lse, ws,
+        B * Sq, (int)Sq, (int)V, ld);
+  else
+    k_ce_fwd_bf16<false><<<grid, 256, 0, S(stream)>>>(
+        (const __bf16*)logits, (const int64_t*)labels, (float*)lse,
+        (float*)loss, B * Sq, (int)Sq, (int)V, ld);
+  OB_LAUNCH_CHECK();
+  if (ws) {
+    k_ce_fold<<<1, 256, 0, S(stream)>>>(ws, B * Sq, (float*)loss);
+    OB_LAUNCH_CHECK();
+  }
+  return 0;
+}
 extern "C" int ob_ce_fwd_bf16(const void* logits, const void* labels,
                               void* lse, void* loss, int64_t B, int64_t Sq,
                               int64_t V, int64_t ld, void* stream) {
-  k_ce_fwd_bf16<<<(int)bmin64(B * Sq, 16384), 256, 0, S(stream)>>>(
-      (const __bf16*)logits, (const int64_t*)labels, (float*)lse,
-      (float*)loss, B * Sq, (int)Sq, (int)V, ld);
+  return ob_ce_fwd_ws(logits, labels, lse, loss, B, Sq, V, ld, nullptr,
+                      stream);
+}
+
+// ob_ce_fwd_bf16 with a run-to-run bit-stable loss; ws: B * Sq floats
+extern "C" int ob_ce_fwd_det_bf16(const void* logits, const void* labels,
+                                  void* lse, void* loss, int64_t B,
+                                  int64_t Sq, int64_t V, int64_t ld, void* ws,
+                                  void* stream) {
+  if (!ws) return ob_fail("ce_fwd_det_bf16: ws required");
+  return ob_ce_fwd_ws(logits, labels, lse, loss, B, Sq, V, ld, (float*)ws,
+                      stream);
+}
+
+// ---------------------------------------------------------------------------
+// Deterministic mode: the fixed-order fold of a partial
+// slab.  dst[c] += fold(part[0..nblk)[c]) with this association, which
+// depends on nblk only: group g (0..7) adds rows g, g + 8, g + 16, ... in
+// ascending order starting from row g's value; the groups' sums are then
+// added in ascending g starting from group 0's (groups beyond nblk do not
+// exist); that total is added to dst[c].  Block = 32 columns x 8 groups;
+// blockIdx.y picks one of up to four vectors whose slabs lie vstride floats
+// apart (a null dst is skipped).  No atomics: one thread owns dst[c].
+// ---------------------------------------------------------------------------
+#define CPF_COLS 32
+#define CPF_GROUPS 8
+__global__ __launch_bounds__(CPF_COLS * CPF_GROUPS) void k_colpart_finish(
+    const float* __restrict__ part, int nblk, int64_t N, int64_t ld,
+    int64_t vstride, float* d0, float* d1, float* d2, float* d3) {
+  __shared__ float red[CPF_GROUPS][CPF_COLS];
+  const int v = blockIdx.y;
+  float* const dst = v == 0 ? d0 : v == 1 ? d1 : v == 2 ? d2 : d3;
+  if (!dst) return;  // block-uniform
+  const float* p = part + (int64_t)v * vstride;
+  const int cl = threadIdx.x & (CPF_COLS - 1), g = threadIdx.x / CPF_COLS;
+  const int64_t c = (int64_t)blockIdx.x * CPF_COLS + cl;
+  float s = 0.f;
+  if (c < N && g < nblk) {
+    s = p[(int64_t)g * ld + c];
+    for (int b = g + CPF_GROUPS; b < nblk; b += CPF_GROUPS)
+      s += p[(int64_t)b * ld + c];
+  }
+  red[g][cl] = s;
+  __syncthreads();
+  if (g == 0 && c < N) {
+    float t = red[0][cl];
+    const int ng = nblk < CPF_GROUPS ? nblk : CPF_GROUPS;
+    for (int k = 1; k < ng; ++k) t += red[k][cl];
+    dst[c] += t;
+  }
+}
+
+static int colpart_finish(const float* part, int64_t nblk, int64_t N,
+                          int64_t ld, int64_t vstride, float* d0, float* d1,
+                          float* d2, float* d3, void* stream) {
+  if (nblk <= 0 || N <= 0) return 0;
+  if (nblk > INT32_MAX) return ob_fail("colpart_finish: nblk too large");
+  const int nv = d3 ? 4 : d2 ? 3 : d1 ? 2 : 1;
+  dim3 grid((unsigned)((N + CPF_COLS - 1) / CPF_COLS), (unsigned)nv);
+  k_colpart_finish<<<grid, CPF_COLS * CPF_GROUPS, 0, S(stream)>>>(
+      part, (int)nblk, N, ld, vstride, d0, d1, d2, d3);
   OB_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int ob_colpart_finish_f32(const void* part, int64_t nblk,
+                                     int64_t N, int64_t ld, void* dst,
+                                     void* stream) {
+  if (!part || !dst) return ob_fail("colpart_finish_f32: null arg");
+  if (ld < N) return ob_fail("colpart_finish_f32: ld < N");
+  return colpart_finish((const float*)part, nblk, N, ld, 0, (float*)dst,
+                        nullptr, nullptr, nullptr, stream);
+}
+
+// host-only: floats of slab a _det entry needs (the grids above)
+extern "C" int64_t ob_det_ws_count(int which, int64_t M, int64_t N) {
+  if (M <= 0 || N <= 0) return 0;
+  const int64_t cs = N % 8 == 0 ? (M + 127) / 128 * N : (M + 255) / 256 * N;
+  switch (which) {
+    case OB_DET_WS_COLSUM:
+      return cs;
+    case OB_DET_WS_GELU:
+      return N % 8 == 0 ? (M + BGC_ROWS - 1) / BGC_ROWS * N : cs;
+    case OB_DET_WS_LN: {
+      if (N >= 512 && N <= 1024)
+        return 4 * bmin64((M + BLNR_ROWS - 1) / BLNR_ROWS, BLNR_MAXGRID) * N;
+      const int64_t ln = 2 * ((M + BLN_CHUNK - 1) / BLN_CHUNK) * N;
+      return ln > cs ? ln : cs;
+    }
+    case OB_DET_WS_DROP_CS:
+      return ob_drop_cs_ws_count(M, N);
+    case OB_DET_WS_CE:
+      return M;
+  }
+  return -1;
 }
 
 __global__ __launch_bounds__(256) void k_ce_bwd_bf16(

@@ -14,6 +14,7 @@
 #include "ob_internal.h"
 #include "ob_philox.h"
 
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <initializer_list>
@@ -50,6 +51,17 @@ struct Workspace {
   float* pd_b = nullptr;   // [B*nh, S, S]
   float* dm1 = nullptr;    // [B, S, H] masked d(hmid), site RESID_ATTN
   float* dm2 = nullptr;    // [B, S, H] masked dout, site RESID_MLP
+  // deterministic mode only (never allocated without it): the partial slabs
+  // of the fixed-order column sums, ONE PER STREAM that can run beside
+  // another -- a slab's producer and its finish are stream-ordered, and no
+  // two streams share one.  det_main: the backward's main stream (dropout
+  // colsum, gelu, LayerNorm backward: used one after the other); det_side:
+  // g_side (the b_qkv colsum); det_fwd: the forward's stream (the CE loss,
+  // which under pp1 overlap runs beside a backward).
+  float* det_main = nullptr;
+  float* det_side = nullptr;
+  float* det_fwd = nullptr;
+  int64_t sz_det_main = 0, sz_det_side = 0, sz_det_fwd = 0;
   int64_t sz_dp = 0, sz_bsh = 0, sz_bsh2 = 0, sz_dqkv = 0, sz_b4h = 0,
           sz_t1 = 0, sz_t2 = 0, sz_s1 = 0, sz_s2 = 0, sz_pd_f = 0,
           sz_pd_b = 0, sz_dm1 = 0, sz_dm2 = 0;
@@ -167,6 +179,29 @@ extern "C" int ob_profile_read(int fam, double* total_ms, long long* count) {
   for (int i = 0; i < ProfFam::RING; i++) prof_drain_slot(f, i);
   *total_ms = f.total_ms;
   *count = f.count;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// deterministic mode (include/oobleck_stage.h): process-wide, default from
+// OB_DETERMINISTIC (read once), frozen by the first layer created
+// ---------------------------------------------------------------------------
+// -1: not set by ob_set_deterministic, the environment's default holds
+static std::atomic<int> g_det{-1};
+static int64_t g_layers_created = 0;
+
+extern "C" int ob_deterministic(void) {
+  static const bool env_on = ob_env_flag("OB_DETERMINISTIC", false);
+  const int v = g_det.load(std::memory_order_relaxed);
+  return v < 0 ? (env_on ? 1 : 0) : v;
+}
+
+extern "C" int ob_set_deterministic(int on) {
+  if (g_layers_created > 0)
+    return ob_fail(
+        "set_deterministic: a layer has already been created in this "
+        "process; set the mode before the first layer");
+  g_det.store(on != 0 ? 1 : 0, std::memory_order_relaxed);
   return 0;
 }
 
@@ -327,6 +362,12 @@ static int layer_create(const ob_layer_desc* d, const ob_dropout_desc* drop,
   if (d->seq_len > 2048)
     return ob_fail("create: seq_len > 2048 unsupported in round 1");
   if (d->n_slots < 1) return ob_fail("create: n_slots < 1");
+  const bool det = ob_deterministic() != 0;
+  if (det && d->dtype != 1)
+    return ob_fail(
+        "create: fp32 layers (dtype 0) are not supported in deterministic "
+        "mode (OB_DETERMINISTIC=1 / ob_set_deterministic): their kernels "
+        "still sum with atomics");
   if (drop) {
     if (!ob_drop_p_ok(drop->embd_pdrop) || !ob_drop_p_ok(drop->resid_pdrop) ||
         !ob_drop_p_ok(drop->attn_pdrop))
@@ -469,8 +510,28 @@ static int layer_create(const ob_layer_desc* d, const ob_dropout_desc* drop,
     if (ws_ensure(&g_ws.dm1, &g_ws.sz_dm1, BSH)) return 1;
     if (ws_ensure(&g_ws.dm2, &g_ws.sz_dm2, BSH)) return 1;
   }
+  // deterministic mode: the slabs, from the _det entries' grids at max_batch
+  if (det && d->kind == OB_KIND_BLOCK) {
+    int64_t m = i64max(ob_det_ws_count(OB_DET_WS_GELU, BS, 4 * H),
+                       ob_det_ws_count(OB_DET_WS_LN, BS, H));
+    if (l->p_resid > 0.f)
+      m = i64max(m, ob_det_ws_count(OB_DET_WS_DROP_CS, BS, H));
+    if (ws_ensure(&g_ws.det_main, &g_ws.sz_det_main, m)) return 1;
+    if (ws_ensure(&g_ws.det_side, &g_ws.sz_det_side,
+                  ob_det_ws_count(OB_DET_WS_COLSUM, BS, 3 * H)))
+      return 1;
+  }
+  if (det && d->kind == OB_KIND_FINAL) {
+    if (ws_ensure(&g_ws.det_main, &g_ws.sz_det_main,
+                  ob_det_ws_count(OB_DET_WS_LN, BS, H)))
+      return 1;
+    if (ws_ensure(&g_ws.det_fwd, &g_ws.sz_det_fwd,
+                  ob_det_ws_count(OB_DET_WS_CE, BS, 1)))
+      return 1;
+  }
   // pick the library GEMMs' solutions by measurement, once per shape and
-  // process (ob_blaslt.hip; a no-op with OB_LT_TUNE=0)
+  // process (ob_blaslt.hip; a no-op with OB_LT_TUNE=0 and in deterministic
+  // mode, where every plan is the heuristic's top-1)
   static const bool no_lt = ob_env_flag("OB_NO_BLASLT", false);
   if (!no_lt) {
     std::vector<ob_lt_shape> shapes;
@@ -478,6 +539,7 @@ static int layer_create(const ob_layer_desc* d, const ob_dropout_desc* drop,
     for (const ob_lt_shape& s : shapes)
       if (ob_lt_tune_shape(s)) return 1;
   }
+  g_layers_created++;
   *out = l;
   return 0;
 }
@@ -878,7 +940,9 @@ static int dw_bf16_ws(const ob_lt_shape& s, const __bf16* act,
   // gout[actw,dyw] += act^T dY, atomically, K = BS split to fill the chip
   ob_bf16_gemm g;
   g.C = gout, g.M = actw, g.N = dyw, g.K = BS, g.ldc = ldc;
-  g.out_kind = 2, g.splitk = pick_splitk(actw, dyw, BS), g.stream = stream;
+  // deterministic mode: one adder per element per launch (split-K 1)
+  g.out_kind = 2, g.stream = stream;
+  g.splitk = ob_deterministic() ? 1 : pick_splitk(actw, dyw, BS);
   if ((actw % 128) || (dyw % 128) || (BS % 128)) {
     g.transA = 1, g.transB = 0;
     g.A = act, g.lda = actw, g.B = dY, g.ldb = dyw;
@@ -1042,9 +1106,12 @@ static int final_forward_bf16(ob_layer* l, int slot, const __bf16* in,
                         nullptr, logits, stream)))
     return 1;
   OB_HIP(hipMemsetAsync(out, 0, sizeof(float), S(stream)));
+  // deterministic mode: the loss through the forward stream's slab
   if (OB_PROF(OB_PF_CE, stream,
-              ob_ce_fwd_bf16(logits, labs, st + l->o_lse, out, B, Sq, V,
-                             l->v_pad, stream)))
+              ob_ce_fwd_ws(logits, labs, st + l->o_lse, out, B, Sq, V,
+                           l->v_pad,
+                           ob_deterministic() ? g_ws.det_fwd : nullptr,
+                           stream)))
     return 1;
   return 0;
 }
@@ -1081,6 +1148,10 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;
   ob_lt_shape lg[LG_BLOCK_N];
   block_gemms(H, BS, !dR, lg);
+  // deterministic mode: the same calls, same places, same streams, with
+  // the stream's slab (null: the atomic kernels)
+  const bool det = ob_deterministic() != 0;
+  float* const wsm = det ? g_ws.det_main : nullptr;
 
   // The dW family (transposes + atomic GEMMs + the qkv bias colsum) has
   // no consumer inside this call and no effect on the dX chain (the other
@@ -1100,7 +1171,7 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     if (OB_PROF(OB_PF_ELEM, stream,
                 ob_drop_scale_colsum(
                     drop_key(l, slot, OB_DROP_RESID_MLP, l->p_resid), 1, dout,
-                    g_ws.dm2, g + bp.b_mlpproj, BS, H, stream)))
+                    g_ws.dm2, g + bp.b_mlpproj, BS, H, stream, wsm)))
       return 1;
     dmlp = (const __bf16*)g_ws.dm2;
     OB_SIDE_FENCE(S(stream), g_side.stream);  // dm2 ready
@@ -1115,8 +1186,8 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     return 1;
   // gelu backward also sums its output columns into the b_fc grad
   if (OB_PROF(OB_PF_ELEM, stream,
-              ob_gelu_bwd_colsum_bf16(u, DY4, DY4, g + bp.b_fc, BS, 4 * H,
-                                      stream)))
+              ob_gelu_bwd_colsum_ws(u, DY4, DY4, g + bp.b_fc, BS, 4 * H, wsm,
+                                    stream)))
     return 1;
   OB_SIDE_FENCE(S(stream), g_side.stream);  // DY4 post-gelu
   if (OB_PROF(OB_PF_GEMM_DW, side,
@@ -1131,12 +1202,12 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   // no entry copy) and sums both streams it holds in registers: dout
   // columns -> b_mlpproj grad, din columns -> b_attnproj grad
   if (OB_PROF(OB_PF_LN, stream,
-              ob_layernorm_bwd_res_bf16(hmid, p + bp.ln2_w, st + l->o_mean2,
-                                        st + l->o_rstd2, DLN, dout, din,
-                                        g + bp.ln2_w, g + bp.ln2_b,
-                                        dR ? nullptr : g + bp.b_mlpproj,
-                                        dR ? nullptr : g + bp.b_attnproj,
-                                        BS, H, stream)))
+              ob_layernorm_bwd_res_ws(hmid, p + bp.ln2_w, st + l->o_mean2,
+                                      st + l->o_rstd2, DLN, dout, din,
+                                      g + bp.ln2_w, g + bp.ln2_b,
+                                      dR ? nullptr : g + bp.b_mlpproj,
+                                      dR ? nullptr : g + bp.b_attnproj,
+                                      BS, H, wsm, stream)))
     return 1;
   // ---- attention projection ----
   const __bf16* dap = din;
@@ -1144,7 +1215,7 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     if (OB_PROF(OB_PF_ELEM, stream,
                 ob_drop_scale_colsum(
                     drop_key(l, slot, OB_DROP_RESID_ATTN, l->p_resid), 1, din,
-                    g_ws.dm1, g + bp.b_attnproj, BS, H, stream)))
+                    g_ws.dm1, g + bp.b_attnproj, BS, H, stream, wsm)))
       return 1;
     dap = (const __bf16*)g_ws.dm1;
   }
@@ -1168,19 +1239,21 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     const float* lseP = st + l->o_p;
     // the dq kernel forms D = rowsum(dO * O) into Dbuf for the dkdv kernel;
     // also adds the b_qkv grad (column sums of DQKV) from its accumulators
+    // (deterministic mode: not asked for; the side-stream colsum below)
+    float* const dbq = det ? nullptr : g + bp.b_qkv;
     if (dA) {
       // regenerates the masks the forward of this slot drew
       if (OB_PROF(OB_PF_FLASH_BWD, stream,
                   ob_flash_bwd_nt_d_drop_bf16(qkv, am, DATT, lseP, Dbuf, DQKV,
-                                              g + bp.b_qkv, B, Sq, H, nh,
+                                              dbq, B, Sq, H, nh,
                                               scale, l->seed, l->layer_id,
                                               l->slot_tick[slot], l->p_attn,
                                               stream)))
         return 1;
     } else if (OB_PROF(OB_PF_FLASH_BWD, stream,
                        ob_flash_bwd_nt_d_bf16(qkv, am, DATT, lseP, Dbuf, DQKV,
-                                              g + bp.b_qkv, B, Sq, H, nh,
-                                              scale, stream)))
+                                              dbq, B, Sq, H, nh, scale,
+                                              stream)))
       return 1;
   } else if (l->flash) {
     const int64_t BSH = BS * H;
@@ -1248,9 +1321,10 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   }
   // ---- QKV projection ----
   OB_SIDE_FENCE(S(stream), g_side.stream);  // DQKV ready
-  if (!flash_nt &&
+  if ((!flash_nt || det) &&
       OB_PROF(OB_PF_ELEM, side,
-              ob_colsum_bf16(DQKV, g + bp.b_qkv, BS, 3 * H, side)))
+              ob_colsum_ws(DQKV, g + bp.b_qkv, BS, 3 * H,
+                           det ? g_ws.det_side : nullptr, side)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DW, side,
               dw_bf16_ws(lg[LG_DW_QKV], ln1, DQKV, g + bp.w_qkv,
@@ -1263,9 +1337,9 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   // ln1 backward accumulates into din: wait for the side's din readers
   OB_HIP(hipStreamWaitEvent(S(stream), ev_din_done, 0));
   if (OB_PROF(OB_PF_LN, stream,
-              ob_layernorm_bwd_bf16(x, p + bp.ln1_w, st + l->o_mean1,
-                                    st + l->o_rstd1, DLN, din, g + bp.ln1_w,
-                                    g + bp.ln1_b, BS, H, 1, stream)))
+              ob_layernorm_bwd_ws(x, p + bp.ln1_w, st + l->o_mean1,
+                                  st + l->o_rstd1, DLN, din, g + bp.ln1_w,
+                                  g + bp.ln1_b, BS, H, 1, wsm, stream)))
     return 1;
   // join: the next call reuses DY4/DQKV/din workspaces on the main stream
   OB_SIDE_FENCE(g_side.stream, S(stream));  // join
@@ -1317,7 +1391,8 @@ static int final_backward_bf16(ob_layer* l, int slot, const float* dout,
       ob_bf16_gemm dw;
       dw.A = DLT, dw.lda = BS, dw.B = LNT, dw.ldb = BS;
       dw.C = g + 2 * H, dw.ldc = H, dw.M = l->v_pad, dw.N = H, dw.K = BS;
-      dw.out_kind = 2, dw.splitk = 2, dw.Mr = V, dw.stream = side;
+      dw.out_kind = 2, dw.splitk = ob_deterministic() ? 1 : 2, dw.Mr = V;
+      dw.stream = side;
       if (OB_PROF(OB_PF_GEMM_DW, side, ob_gemm_bf16_nt_dispatch(dw)))
         return 1;
     }
@@ -1328,9 +1403,10 @@ static int final_backward_bf16(ob_layer* l, int slot, const float* dout,
                         nullptr, nullptr, DLN, stream)))
     return 1;
   if (OB_PROF(OB_PF_LN, stream,
-              ob_layernorm_bwd_bf16(x, p + 0, st + l->o_mean1,
-                                    st + l->o_rstd1, DLN, din, g + 0, g + H,
-                                    BS, H, 0, stream)))
+              ob_layernorm_bwd_ws(x, p + 0, st + l->o_mean1, st + l->o_rstd1,
+                                  DLN, din, g + 0, g + H, BS, H, 0,
+                                  ob_deterministic() ? g_ws.det_main : nullptr,
+                                  stream)))
     return 1;
   // join: the next backward reuses s1/s2 and reads g on the main stream
   OB_SIDE_FENCE(g_side.stream, S(stream));  // join
@@ -1564,6 +1640,13 @@ extern "C" int ob_layer_backward(ob_layer_t l, int32_t slot, const void* dout,
     case OB_KIND_EMBED: {
       const int64_t Sq = l->d.seq_len, H = l->d.n_embd, V = l->d.vocab_size;
       int64_t* ids = l->ids + (int64_t)slot * (int64_t)l->d.max_batch * Sq;
+      if (ob_deterministic()) {  // bf16 only: create refuses fp32
+        const ob_drop_key ke = drop_key(l, slot, OB_DROP_EMBD, l->p_embd);
+        return OB_PROF(OB_PF_ELEM, stream,
+                       ob_embed_bwd_det(l->slot_drop[slot] ? &ke : nullptr,
+                                        ids, dout, l->grads, l->grads + V * H,
+                                        l->B, Sq, H, stream));
+      }
       if (l->slot_drop[slot])
         return OB_PROF(OB_PF_ELEM, stream,
                        ob_embed_bwd_drop(

@@ -93,6 +93,7 @@ class Layer:
             check(ext.ob_layer_create(ctypes.byref(self._desc),
                                       ctypes.byref(handle)), "layer_create")
         self._h = handle
+        self._deterministic = bool(ext.ob_deterministic())
         self.training = True
         self._sharded = None
         if group_size > 1:
@@ -139,6 +140,12 @@ class Layer:
             check(get_ext().ob_layer_refresh_weights(self._h, _stream_ptr()),
                   f"refresh_weights layer {self.layer_id}")
             self._shadows_stale = False
+
+    @property
+    def deterministic(self) -> bool:
+        """Whether this layer was created in deterministic mode (the mode is
+        process-wide and frozen by the first layer created)."""
+        return self._deterministic
 
     @property
     def uses_flash(self) -> bool:

@@ -111,10 +111,14 @@ class PipelineExecution:
         # H2D staging and per-microbatch device allocations on a side
         # stream (fixed by pinned + per-slot buffers here).  Measured:
         # 246.5 ms/step vs 267.8 without (+8.6%).  OB_PP1_OVERLAP=0
-        # disables.
+        # disables.  Deterministic mode runs without it:
+        # with the two streams side by side two runs differ from the first
+        # step's forward on, from a source not yet found, and agree bit for
+        # bit without.
         import os
         self._overlap = (
             os.environ.get("OB_PP1_OVERLAP", "1") == "1"
+            and not any(getattr(l, "deterministic", False) for l in layers)
             and pipeline.device.type == "cuda"
             and pipeline.is_first_stage() and pipeline.is_last_stage()
             and not any(getattr(l, "_sharded", None) is not None
@@ -504,6 +508,11 @@ class OobleckPipeline:
             "labels": [None] * n_slots,
             "outputs": [None] * n_slots,
         }
+        if self.training_cfg.deterministic:
+            # process-wide, and only settable before the first layer exists
+            from ._ext import deterministic, set_deterministic
+            if not deterministic():
+                set_deterministic(True)
         layers = [layer_factory(lid, self._per_layer_pgs[lid], n_slots)
                   for lid in my_layers]
         optimizer, lr_sched = optimizer_factory(layers)
