@@ -119,6 +119,26 @@ int ob_layer_uses_flash(ob_layer_t l);
  * no GPU call. */
 int ob_flash_eligible(const ob_layer_desc* desc, float attn_pdrop);
 
+/* The device memory ob_layer_create_ex takes for `desc` (drop may be null),
+ * from the same table the create allocates by (DESIGN.md "Layer memory").
+ * modes: bit 0 deterministic, 1 OB_BF16_FLASH, 2 OB_FLASH_TR, 3
+ * OB_FLASH_DROP, 4 OB_FLASH_HD128 (a set bit = that switch on); -1 = this
+ * process's.  Writes up to cap int64s and returns the field count (-1 on a
+ * null argument).  Fields, in order: flash, side (needs the side stream),
+ * v_pad, slot_stride (floats of one stash slot), ids_count (int64s, all
+ * slots), shadow_count (bf16 elements); the 15 stash regions' offsets within
+ * a slot, then their lengths (floats; x, mean1, rstd1, ln1, qkv, p, attnm,
+ * hmid, mean2, rstd2, ln2, u, g, logits, lse; length 0 = not of this kind);
+ * the 10 shadows' offsets (bf16 elements; qkv, qkv_t, ap, ap_t, fc, fc_t,
+ * mp, mp_t, lm, lm_t); the floats needed of each of the 16 shared workspace
+ * buffers (0 = not used; dp, dln, datt, dqkv, dy4, flash_bwd, flash_vt, dw_a,
+ * dw_b, pd_fwd, pd_bwd, dm_attn, dm_mlp, det_main, det_side, det_fwd); the
+ * layout of flash_bwd under OB_FLASH_TR=0: offsets of Q^T, K^T, dO^T (bf16
+ * elements) and of D (floats).  Host-only, no GPU call. */
+int ob_layer_plan_query(const ob_layer_desc* desc,
+                        const ob_dropout_desc* drop, int modes, int64_t* out,
+                        int cap);
+
 /* Training mode (default 1).  0 makes dropout inert (eval): forwards run
  * today's dropout-free path and do not advance the tick. */
 int ob_layer_set_training(ob_layer_t l, int on);

@@ -56,6 +56,9 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.ob_layer_set_training.argtypes = [vp, i32]
     lib.ob_layer_uses_flash.argtypes = [vp]
     lib.ob_flash_eligible.argtypes = [ctypes.POINTER(ObLayerDesc), f32]
+    lib.ob_layer_plan_query.argtypes = [ctypes.POINTER(ObLayerDesc),
+                                        ctypes.POINTER(ObDropoutDesc), i32,
+                                        ctypes.POINTER(i64), i32]
     lib.ob_layer_set_dropout_tick.argtypes = [vp, u64]
     # (seed, layer_id, site, tick, p) select the mask of every dropout entry
     key = [u64, i32, i32, u64, f32]
@@ -277,6 +280,41 @@ def lt_candidates(shape, cap: int = 128) -> list[dict]:
     n = get_ext().ob_gemm_lt_candidates(lt_shape(*shape), idx, pos, us, cap)
     return [{"index": idx[i], "pos": pos[i], "us": us[i]}
             for i in range(max(0, min(n, cap)))]
+
+
+# ob_layer_plan_query's fields, in order (include/oobleck_stage.h)
+PLAN_STASH = ("x", "mean1", "rstd1", "ln1", "qkv", "p", "attnm", "hmid",
+              "mean2", "rstd2", "ln2", "u", "g", "logits", "lse")
+PLAN_SHADOWS = ("qkv", "qkv_t", "ap", "ap_t", "fc", "fc_t", "mp", "mp_t",
+                "lm", "lm_t")
+PLAN_WS = ("dp", "dln", "datt", "dqkv", "dy4", "flash_bwd", "flash_vt",
+           "dw_a", "dw_b", "pd_fwd", "pd_bwd", "dm_attn", "dm_mlp",
+           "det_main", "det_side", "det_fwd")
+LAYER_PLAN_NAMES = (
+    ("flash", "side", "v_pad", "slot_stride", "ids_count", "shadow_count")
+    + tuple(f"st_off_{n}" for n in PLAN_STASH)
+    + tuple(f"st_len_{n}" for n in PLAN_STASH)
+    + tuple(f"sh_off_{n}" for n in PLAN_SHADOWS)
+    + tuple(f"ws_{n}" for n in PLAN_WS)
+    + ("pk_qt", "pk_kt", "pk_dot", "pk_d"))
+# bits of ob_layer_plan_query's modes
+PLAN_DET, PLAN_BF16_FLASH, PLAN_FLASH_TR, PLAN_FLASH_DROP, PLAN_FLASH_HD128 = (
+    1, 2, 4, 8, 16)
+
+
+def layer_plan(desc: ObLayerDesc, drop: ObDropoutDesc | None = None,
+               modes: int = -1) -> dict:
+    """The device memory ob_layer_create_ex takes for a description: stash
+    layout, shadows and the share of the workspace (DESIGN.md "Layer
+    memory").  No GPU call."""
+    n = len(LAYER_PLAN_NAMES)
+    buf = (ctypes.c_int64 * n)()
+    got = get_ext().ob_layer_plan_query(
+        ctypes.byref(desc), ctypes.byref(drop) if drop else None, modes, buf,
+        n)
+    if got != n:
+        raise RuntimeError(f"ob_layer_plan_query returned {got}, not {n}")
+    return dict(zip(LAYER_PLAN_NAMES, buf))
 
 
 # which-codes of ob_det_ws_count (OB_DET_WS_* of include/oobleck_stage.h)

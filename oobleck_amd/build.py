@@ -18,6 +18,7 @@ SOURCES = [PKG_DIR / "csrc" / "ob_kernels.hip",
            PKG_DIR / "csrc" / "ob_layer.hip"]
 HEADERS = [PKG_DIR.parent / "include" / "oobleck_stage.h",
            PKG_DIR / "csrc" / "ob_internal.h",
+           PKG_DIR / "csrc" / "ob_layer_plan.h",
            PKG_DIR / "csrc" / "ob_flash_fold.h",
            PKG_DIR / "csrc" / "ob_flash_common.h",
            PKG_DIR / "csrc" / "ob_bf16.h",

@@ -12,61 +12,31 @@
 // flight, matching deepspeed-style pipe buffers (pipeline.py:556-562).
 #include "ob_gemm_route.h"
 #include "ob_internal.h"
+#include "ob_layer_plan.h"
 #include "ob_philox.h"
 
 #include <atomic>
 #include <cmath>
 #include <cstring>
 #include <initializer_list>
+#include <memory>
 #include <vector>
 
 static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-static inline int64_t i64min(int64_t a, int64_t b) { return a < b ? a : b; }
-static inline int64_t i64max(int64_t a, int64_t b) { return a > b ? a : b; }
 
 // ---------------------------------------------------------------------------
-// shared backward workspace (single driving thread per GPU by ABI contract)
+// shared workspace (single driving thread per GPU by ABI contract)
 // ---------------------------------------------------------------------------
 
-struct Workspace {
-  float* dp = nullptr;     // [B*nh, S, S]
-  float* bsh1 = nullptr;   // [B, S, H]
-  float* bsh2 = nullptr;   // [B, S, H]
-  float* dqkv = nullptr;   // [B, S, 3H]
-  float* b4h = nullptr;    // [B, S, 4H]
-  float* t1 = nullptr;     // flash backward: D [B*nh, S]; with OB_FLASH_TR=0
-  float* t2 = nullptr;     // also the bf16 transposed operands (t2: fwd V^T)
-  float* s1 = nullptr;     // side-stream dW transpose buffers (bf16 as
-  float* s2 = nullptr;     // floats): the dW family runs on g_side
-  // dropout only (never allocated without it); pd_f / pd_b only for
-  // attention dropout on the materialized-P path (a flash layer regenerates
-  // its masks in the flash kernels and owns no [B*nh, S, S] buffer).  pd_f
-  // belongs to the FORWARD (Pd = drop(P) feeding the PV GEMM): under pp1
-  // overlap a forward runs beside a backward, so it shares nothing with the
-  // buffers below.
-  // pd_b is the backward's regenerated Pd; dm1/dm2 hold the masked
-  // projection grads, which the side-stream dW GEMMs read until the
-  // end-of-call join (DATT/DLN are overwritten by the main stream earlier).
-  float* pd_f = nullptr;   // [B*nh, S, S]
-  float* pd_b = nullptr;   // [B*nh, S, S]
-  float* dm1 = nullptr;    // [B, S, H] masked d(hmid), site RESID_ATTN
-  float* dm2 = nullptr;    // [B, S, H] masked dout, site RESID_MLP
-  // deterministic mode only (never allocated without it): the partial slabs
-  // of the fixed-order column sums, ONE PER STREAM that can run beside
-  // another -- a slab's producer and its finish are stream-ordered, and no
-  // two streams share one.  det_main: the backward's main stream (dropout
-  // colsum, gelu, LayerNorm backward: used one after the other); det_side:
-  // g_side (the b_qkv colsum); det_fwd: the forward's stream (the CE loss,
-  // which under pp1 overlap runs beside a backward).
-  float* det_main = nullptr;
-  float* det_side = nullptr;
-  float* det_fwd = nullptr;
-  int64_t sz_det_main = 0, sz_det_side = 0, sz_det_fwd = 0;
-  int64_t sz_dp = 0, sz_bsh = 0, sz_bsh2 = 0, sz_dqkv = 0, sz_b4h = 0,
-          sz_t1 = 0, sz_t2 = 0, sz_s1 = 0, sz_s2 = 0, sz_pd_f = 0,
-          sz_pd_b = 0, sz_dm1 = 0, sz_dm2 = 0;
-};
-static Workspace g_ws;
+// buffers and sizes (floats) by WS_* of ob_layer_plan.h, which says what each
+// one holds and which stream owns it; grown at create, never shrunk
+static struct {
+  float* buf[WS_N];
+  int64_t size[WS_N];
+} g_ws;
+// the one place a workspace buffer gets its element type
+template <class T>
+static T* ws(int i) { return reinterpret_cast<T*>(g_ws.buf[i]); }
 
 // side stream + events for overlapping the weight-grad family (dW
 // transposes + atomic GEMMs + bias colsums: HBM-heavy, independent of
@@ -224,28 +194,18 @@ struct ob_layer {
   int B;                    // current microbatch size (<= max_batch)
   float* params = nullptr;  // caller-owned flat fp32
   float* grads = nullptr;
-  // stash (extension-owned), one contiguous allocation, slot-strided
+  // what this layer owns and shares, and where (ob_layer_plan.h)
+  ob_layer_plan plan;
+  // stash (extension-owned), one contiguous allocation, slot-strided.  A
+  // bf16 layer keeps the fp32-sized regions and its data occupies the first
+  // half of each (2x overcommit, traded for zero layout churn; memory is
+  // plentiful at 288 GB).
   float* stash = nullptr;
-  int64_t slot_stride = 0;  // floats per slot
   int64_t* ids = nullptr;   // EMBED: [n_slots, B*S]; FINAL: labels
-  // per-kind offsets into stash (floats, within a slot)
-  int64_t o_x = 0, o_mean1 = 0, o_rstd1 = 0, o_ln1 = 0, o_qkv = 0, o_p = 0,
-          o_attnm = 0, o_hmid = 0, o_mean2 = 0, o_rstd2 = 0, o_ln2 = 0,
-          o_u = 0, o_g = 0, o_logits = 0, o_lse = 0;
   // bf16 mode (d.dtype == 1): weight shadows in plain + transposed layouts
   // so every GEMM operand has k contiguous in memory (see
-  // ob_gemm_bf16.hip header).  The stash keeps its fp32-sized offsets
-  // and bf16 data occupies the first half of each region (2x overcommit,
-  // traded for zero layout churn; memory is plentiful at 288 GB).
+  // ob_gemm_bf16.hip header)
   __bf16* shadows = nullptr;
-  int64_t v_pad = 0;  // vocab rounded up to 8 (16-byte bf16 alignment)
-  int64_t sh_qkv = 0, sh_qkv_t = 0, sh_ap = 0, sh_ap_t = 0, sh_fc = 0,
-          sh_fc_t = 0, sh_mp = 0, sh_mp_t = 0, sh_lm = 0, sh_lm_t = 0;
-  int64_t shadow_count = 0;
-  // fused flash-attention path (bf16, head_dim 64 or 128, S % 128 == 0): the
-  // o_p slot holds only the per-row LSE ([Bm*nh, S] floats) instead of
-  // the materialized [Bm*nh, S, S] P.
-  bool flash = false;
   // dropout (ob_layer_create_ex); all probabilities 0 = none.  Only the
   // probabilities that apply to this layer's kind are kept.
   float p_embd = 0.f, p_resid = 0.f, p_attn = 0.f;
@@ -267,6 +227,61 @@ static ob_drop_key drop_key(const ob_layer* l, int slot, int site, float p) {
   return ob_drop_make_key(l->seed, l->layer_id, site, l->slot_tick[slot], p);
 }
 
+// The views: the one place a stash region, a shadow or this slot's ids get
+// their address and element type (T: float, or __bf16 for a bf16 layer).
+template <class T>
+static T* st_at(const ob_layer* l, int slot, int region) {
+  return reinterpret_cast<T*>(l->stash + (int64_t)slot * l->plan.slot_stride +
+                              l->plan.st_off[region]);
+}
+static __bf16* shadow(const ob_layer* l, int which) {
+  return l->shadows + l->plan.sh_off[which];
+}
+static int64_t* slot_ids(const ob_layer* l, int slot) {
+  return l->ids + (int64_t)slot * l->d.max_batch * l->d.seq_len;
+}
+template <class T>
+struct BlockStash {
+  T *x, *ln1, *qkv, *P, *am, *hmid, *ln2, *u, *gact;
+  float *mean1, *rstd1, *mean2, *rstd2;
+  float* lseP;  // a flash layer's row LSE, kept where P would be
+  BlockStash(const ob_layer* l, int s)
+      : x(st_at<T>(l, s, ST_X)), ln1(st_at<T>(l, s, ST_LN1)),
+        qkv(st_at<T>(l, s, ST_QKV)), P(st_at<T>(l, s, ST_P)),
+        am(st_at<T>(l, s, ST_ATTNM)), hmid(st_at<T>(l, s, ST_HMID)),
+        ln2(st_at<T>(l, s, ST_LN2)), u(st_at<T>(l, s, ST_U)),
+        gact(st_at<T>(l, s, ST_G)), mean1(st_at<float>(l, s, ST_MEAN1)),
+        rstd1(st_at<float>(l, s, ST_RSTD1)),
+        mean2(st_at<float>(l, s, ST_MEAN2)),
+        rstd2(st_at<float>(l, s, ST_RSTD2)), lseP(st_at<float>(l, s, ST_P)) {}
+};
+template <class T>
+struct FinalStash {
+  T *x, *lnf, *logits;  // the backward turns logits into dlogits in place
+  float *mean, *rstd, *lse;
+  int64_t* labs;
+  FinalStash(const ob_layer* l, int s)
+      : x(st_at<T>(l, s, ST_X)), lnf(st_at<T>(l, s, ST_LN1)),
+        logits(st_at<T>(l, s, ST_LOGITS)), mean(st_at<float>(l, s, ST_MEAN1)),
+        rstd(st_at<float>(l, s, ST_RSTD1)), lse(st_at<float>(l, s, ST_LSE)),
+        labs(slot_ids(l, s)) {}
+};
+// the backward's workspace (WS_* of ob_layer_plan.h)
+template <class T>
+struct BwdWs {
+  T *DY4, *DLN, *DATT, *DQKV, *DP, *pd, *dm1, *dm2;
+  T *QT, *KT, *dOT;  // OB_FLASH_TR=0 only
+  float* D;          // flash backward's rowsum(dO * O)
+  explicit BwdWs(const ob_layer* l)
+      : DY4(ws<T>(WS_DY4)), DLN(ws<T>(WS_DLN)), DATT(ws<T>(WS_DATT)),
+        DQKV(ws<T>(WS_DQKV)), DP(ws<T>(WS_DP)), pd(ws<T>(WS_PD_BWD)),
+        dm1(ws<T>(WS_DM_ATTN)), dm2(ws<T>(WS_DM_MLP)),
+        QT(ws<T>(WS_FLASH_BWD) + l->plan.pk_qt),
+        KT(ws<T>(WS_FLASH_BWD) + l->plan.pk_kt),
+        dOT(ws<T>(WS_FLASH_BWD) + l->plan.pk_dot),
+        D(ws<float>(WS_FLASH_BWD) + l->plan.pk_d) {}
+};
+
 // The flash path reads its column-major MFMA operands from the row-major LDS
 // tiles (ob_flash_*_nt_bf16): no V^T / Q^T / K^T / dO^T copies, and the
 // b_qkv bias grad comes from the backward kernels' accumulators.
@@ -275,45 +290,46 @@ static bool flash_tr() {
   static const bool on = ob_env_flag("OB_FLASH_TR", true);
   return on;
 }
-
-// Attention dropout inside the flash kernels (ob_flash_*_nt_drop_bf16).
-// OB_FLASH_DROP=0 (read once) sends attn_pdrop > 0 to the materialized-P
-// path instead, as before those kernels existed.
-static bool flash_drop() {
-  static const bool on = ob_env_flag("OB_FLASH_DROP", true);
+// OB_NO_BLASLT=1 (read once) keeps every GEMM on the hand-written kernels
+static bool no_blaslt() {
+  static const bool on = ob_env_flag("OB_NO_BLASLT", false);
   return on;
 }
 
-// Fused attention at head_dim 128 (ob_flash_hd128_bf16.hip).
-// OB_FLASH_HD128=0 (read once) keeps such a layer on the materialized-P
-// path, as before those kernels existed.
-static bool flash_hd128() {
-  static const bool on = ob_env_flag("OB_FLASH_HD128", true);
-  return on;
+// This process's modes.  OB_BF16_FLASH=0 keeps every layer on the
+// materialized-P path; OB_FLASH_DROP=0 sends attn_pdrop > 0 there, and
+// OB_FLASH_HD128=0 head_dim 128, as before those kernels existed
+// (ob_flash_*_nt_drop_bf16, ob_flash_hd128_bf16.hip).  All read once.
+static ob_layer_modes process_modes() {
+  static const bool fl = ob_env_flag("OB_BF16_FLASH", true),
+                    drop = ob_env_flag("OB_FLASH_DROP", true),
+                    hd128 = ob_env_flag("OB_FLASH_HD128", true);
+  return {ob_deterministic() != 0, fl, flash_tr(), drop, hd128};
 }
-
-// flash applies to bf16 layers with n_embd % n_head == 0, head_dim 64 (GPT-2
-// small and XL) or 128 (the GPT-3 sizes from 1.3B up) and S % 128 == 0;
-// OB_BF16_FLASH=0 falls back to the materialized-P path.  head_dim 128 has
-// production kernels only: no OB_FLASH_TR=0 twins and no dropout variant.
-// Decided at create time: it sizes the stash.
-static bool flash_eligible(const ob_layer_desc* d, float attn_pdrop = 0.f) {
-  // only the production kernels have a dropout variant, not the
-  // OB_FLASH_TR=0 twins
-  if (attn_pdrop > 0.f && !(flash_tr() && flash_drop())) return false;
-  static const bool on = ob_env_flag("OB_BF16_FLASH", true);
-  if (!on || d->dtype != 1 || d->n_head <= 0 || d->n_embd % d->n_head ||
-      d->seq_len <= 0 || d->seq_len % 128)
-    return false;
-  const int64_t hd = d->n_embd / d->n_head;
-  if (hd == 128) return attn_pdrop == 0.f && flash_tr() && flash_hd128();
-  return hd == 64;
+static ob_layer_modes modes_of_bits(int bits) {
+  if (bits < 0) return process_modes();
+  return {(bits & 1) != 0, (bits & 2) != 0, (bits & 4) != 0, (bits & 8) != 0,
+          (bits & 16) != 0};
 }
 
 // the decision ob_layer_create_ex takes for `d` with this attn_pdrop; host
 // only, no GPU call
 extern "C" int ob_flash_eligible(const ob_layer_desc* d, float attn_pdrop) {
-  return d && flash_eligible(d, attn_pdrop) ? 1 : 0;
+  return d && ob_layer_plan_of(*d, 0.f, attn_pdrop, process_modes()).flash;
+}
+
+extern "C" int ob_layer_plan_query(const ob_layer_desc* d,
+                                   const ob_dropout_desc* drop, int modes,
+                                   int64_t* out, int cap) {
+  if (!d || (!out && cap > 0)) return -1;
+  const ob_layer_plan p =
+      ob_layer_plan_of(*d, drop ? drop->resid_pdrop : 0.f,
+                       drop ? drop->attn_pdrop : 0.f, modes_of_bits(modes));
+  if (p.error) return ob_fail("plan_query: %s", p.error), -1;
+  int64_t f[OB_LAYER_PLAN_FIELDS];
+  ob_layer_plan_fields(p, f);
+  for (int i = 0; i < OB_LAYER_PLAN_FIELDS && i < cap; i++) out[i] = f[i];
+  return OB_LAYER_PLAN_FIELDS;
 }
 
 // parameter offsets (canonical layout, oracle/gpt2_oracle.py::layer_param_spec)
@@ -352,8 +368,10 @@ extern "C" int64_t ob_layer_param_count(const ob_layer_desc* d) {
 
 static void ob_layer_lt_list(const ob_layer_desc* d, bool resid_drop,
                              std::vector<ob_lt_shape>* out);
-// vocab rows of the lm_head shadows, logits and their GEMMs
-static int64_t v_pad_of(int64_t V) { return (V + 255) / 256 * 256; }
+
+struct layer_deleter {
+  void operator()(ob_layer* l) const { ob_layer_destroy(l); }
+};
 
 static int layer_create(const ob_layer_desc* d, const ob_dropout_desc* drop,
                         ob_layer_t* out) {
@@ -375,7 +393,9 @@ static int layer_create(const ob_layer_desc* d, const ob_dropout_desc* drop,
     if (drop->layer_id < 0 || drop->layer_id >= (1 << 24))
       return ob_fail("create_ex: layer_id out of range");
   }
-  ob_layer* l = new ob_layer();
+  // every failure from here on frees what the layer took so far
+  std::unique_ptr<ob_layer, layer_deleter> guard(new ob_layer());
+  ob_layer* const l = guard.get();
   l->d = *d;
   l->B = d->max_batch;
   l->slot_drop.assign(d->n_slots, 0);
@@ -389,158 +409,39 @@ static int layer_create(const ob_layer_desc* d, const ob_dropout_desc* drop,
     l->layer_id = drop->layer_id;
     l->seed = drop->seed;
   }
-  const int64_t Bm = d->max_batch, Sq = d->seq_len, H = d->n_embd,
-                nh = d->n_head, V = d->vocab_size;
-  const int64_t BS = Bm * Sq, BSH = BS * H;
-  int64_t o = 0;
-  switch (d->kind) {
-    case OB_KIND_EMBED:
-      l->slot_stride = 0;
-      break;
-    case OB_KIND_BLOCK:
-      l->o_x = o; o += BSH;
-      l->o_mean1 = o; o += BS;
-      l->o_rstd1 = o; o += BS;
-      l->o_ln1 = o; o += BSH;
-      l->o_qkv = o; o += BS * 3 * H;
-      l->flash = flash_eligible(d, l->p_attn);
-      l->o_p = o; o += l->flash ? Bm * nh * Sq : Bm * nh * Sq * Sq;
-      l->o_attnm = o; o += BSH;
-      l->o_hmid = o; o += BSH;
-      l->o_mean2 = o; o += BS;
-      l->o_rstd2 = o; o += BS;
-      l->o_ln2 = o; o += BSH;
-      l->o_u = o; o += BS * 4 * H;
-      l->o_g = o; o += BS * 4 * H;
-      l->slot_stride = o;
-      break;
-    case OB_KIND_FINAL:
-      l->o_x = o; o += BSH;
-      l->o_mean1 = o; o += BS;
-      l->o_rstd1 = o; o += BS;
-      l->o_ln1 = o; o += BSH;
-      l->o_logits = o; o += BS * V;
-      l->o_lse = o; o += BS;
-      l->slot_stride = o;
-      break;
+  const ob_layer_plan& pl = l->plan =
+      ob_layer_plan_of(*d, l->p_resid, l->p_attn, process_modes());
+  if (pl.error) return ob_fail("create: %s", pl.error);
+  if (pl.slot_stride > 0 &&
+      hipMalloc(&l->stash, (size_t)pl.slot_stride * d->n_slots *
+                               sizeof(float)) != hipSuccess)
+    return ob_fail("create: stash hipMalloc of %lld floats failed",
+                   (long long)(pl.slot_stride * d->n_slots));
+  if (pl.ids_count > 0 &&
+      hipMalloc(&l->ids, (size_t)pl.ids_count * sizeof(int64_t)) !=
+          hipSuccess)
+    return ob_fail("create: ids hipMalloc failed");
+  if (pl.shadow_count > 0) {
+    if (hipMalloc(&l->shadows, (size_t)pl.shadow_count * sizeof(__bf16)) !=
+        hipSuccess)
+      return ob_fail("create: shadow hipMalloc failed");
+    OB_HIP(hipMemset(l->shadows, 0, (size_t)pl.shadow_count * sizeof(__bf16)));
   }
-  if (l->slot_stride > 0) {
-    if (hipMalloc(&l->stash, (size_t)l->slot_stride * d->n_slots *
-                                 sizeof(float)) != hipSuccess) {
-      delete l;
-      return ob_fail("create: stash hipMalloc of %lld floats failed",
-                     (long long)(l->slot_stride * d->n_slots));
-    }
-  }
-  if (d->kind == OB_KIND_EMBED || d->kind == OB_KIND_FINAL) {
-    if (hipMalloc(&l->ids, (size_t)BS * d->n_slots * sizeof(int64_t)) !=
-        hipSuccess) {
-      if (l->stash) hipFree(l->stash);
-      delete l;
-      return ob_fail("create: ids hipMalloc failed");
-    }
-  }
-  // pad vocab to a 256 multiple: makes the lm_head GEMM family
-  // (logits fwd, d_lnout, dW_lm via transposes) interior shapes for
-  // the glds path AND the 256^2 8-phase kernel (gpt2's 50257 at 128
-  // padding lands on 50304 % 256 != 0); shadow pad rows stay zero so
-  // padded logits/grads are exactly zero
-  l->v_pad = v_pad_of(V);
-  if (d->dtype == 1) {
-    int64_t o2 = 0;
-    if (d->kind == OB_KIND_BLOCK) {
-      l->sh_qkv = o2; o2 += 3 * H * H;
-      l->sh_qkv_t = o2; o2 += 3 * H * H;
-      l->sh_ap = o2; o2 += H * H;
-      l->sh_ap_t = o2; o2 += H * H;
-      l->sh_fc = o2; o2 += 4 * H * H;
-      l->sh_fc_t = o2; o2 += 4 * H * H;
-      l->sh_mp = o2; o2 += 4 * H * H;
-      l->sh_mp_t = o2; o2 += 4 * H * H;
-    } else if (d->kind == OB_KIND_FINAL) {
-      l->sh_lm = o2; o2 += l->v_pad * H;   // pad rows zeroed at alloc
-      l->sh_lm_t = o2; o2 += H * l->v_pad;
-    }
-    l->shadow_count = o2;
-    if (o2 > 0) {
-      if (hipMalloc(&l->shadows, (size_t)o2 * sizeof(__bf16)) != hipSuccess)
-        return ob_fail("create: shadow hipMalloc failed");
-      OB_HIP(hipMemset(l->shadows, 0, (size_t)o2 * sizeof(__bf16)));
-    }
-  }
-  // grow the shared backward workspace
-  if (d->kind == OB_KIND_BLOCK) {
-    if (!l->flash &&
-        ws_ensure(&g_ws.dp, &g_ws.sz_dp, Bm * nh * Sq * Sq))
-      return 1;
-    if (ws_ensure(&g_ws.dqkv, &g_ws.sz_dqkv, BS * 3 * H)) return 1;
-    if (ws_ensure(&g_ws.b4h, &g_ws.sz_b4h, BS * 4 * H)) return 1;
-    if (d->dtype == 1) {
-      if (l->flash && flash_tr()) {
-        // only the flash backward's D = rowsum(dO * O), [Bm*nh, S] floats
-        if (ws_ensure(&g_ws.t1, &g_ws.sz_t1, Bm * nh * Sq)) return 1;
-      } else {
-        if (ws_ensure(&g_ws.t1, &g_ws.sz_t1, (4 * H * BS + 1) / 2)) return 1;
-        if (ws_ensure(&g_ws.t2, &g_ws.sz_t2, (4 * H * BS + 1) / 2)) return 1;
-      }
-      if (ws_ensure(&g_ws.s1, &g_ws.sz_s1, (4 * H * BS + 1) / 2)) return 1;
-      if (ws_ensure(&g_ws.s2, &g_ws.sz_s2, (4 * H * BS + 1) / 2)) return 1;
-      if (side_init()) return 1;
-    }
-  }
-  if (d->kind == OB_KIND_FINAL && d->dtype == 1) {
-    if (ws_ensure(&g_ws.t1, &g_ws.sz_t1, (l->v_pad * BS + 1) / 2)) return 1;
-    if (ws_ensure(&g_ws.t2, &g_ws.sz_t2, (4 * H * BS + 1) / 2)) return 1;
-    if (ws_ensure(&g_ws.s1, &g_ws.sz_s1, (l->v_pad * BS + 1) / 2)) return 1;
-    if (ws_ensure(&g_ws.s2, &g_ws.sz_s2, (4 * H * BS + 1) / 2)) return 1;
-    if (side_init()) return 1;
-  }
-  if (d->kind != OB_KIND_EMBED) {
-    const int64_t need = BSH;
-    if (ws_ensure(&g_ws.bsh1, &g_ws.sz_bsh, need)) return 1;
-    if (ws_ensure(&g_ws.bsh2, &g_ws.sz_bsh2, need)) return 1;
-  }
-  // dropout workspaces (sized in floats; bf16 uses the first half); a flash
-  // layer draws its attention masks in the flash kernels and needs none
-  if (l->p_attn > 0.f && !l->flash) {
-    if (ws_ensure(&g_ws.pd_f, &g_ws.sz_pd_f, Bm * nh * Sq * Sq)) return 1;
-    if (ws_ensure(&g_ws.pd_b, &g_ws.sz_pd_b, Bm * nh * Sq * Sq)) return 1;
-  }
-  if (l->p_resid > 0.f) {
-    if (ws_ensure(&g_ws.dm1, &g_ws.sz_dm1, BSH)) return 1;
-    if (ws_ensure(&g_ws.dm2, &g_ws.sz_dm2, BSH)) return 1;
-  }
-  // deterministic mode: the slabs, from the _det entries' grids at max_batch
-  if (det && d->kind == OB_KIND_BLOCK) {
-    int64_t m = i64max(ob_det_ws_count(OB_DET_WS_GELU, BS, 4 * H),
-                       ob_det_ws_count(OB_DET_WS_LN, BS, H));
-    if (l->p_resid > 0.f)
-      m = i64max(m, ob_det_ws_count(OB_DET_WS_DROP_CS, BS, H));
-    if (ws_ensure(&g_ws.det_main, &g_ws.sz_det_main, m)) return 1;
-    if (ws_ensure(&g_ws.det_side, &g_ws.sz_det_side,
-                  ob_det_ws_count(OB_DET_WS_COLSUM, BS, 3 * H)))
-      return 1;
-  }
-  if (det && d->kind == OB_KIND_FINAL) {
-    if (ws_ensure(&g_ws.det_main, &g_ws.sz_det_main,
-                  ob_det_ws_count(OB_DET_WS_LN, BS, H)))
-      return 1;
-    if (ws_ensure(&g_ws.det_fwd, &g_ws.sz_det_fwd,
-                  ob_det_ws_count(OB_DET_WS_CE, BS, 1)))
-      return 1;
-  }
+  // grow the shared workspace to this layer's needs
+  for (int i = 0; i < WS_N; i++)
+    if (ws_ensure(&g_ws.buf[i], &g_ws.size[i], pl.ws[i])) return 1;
+  if (pl.side && side_init()) return 1;
   // pick the library GEMMs' solutions by measurement, once per shape and
   // process (ob_blaslt.hip; a no-op with OB_LT_TUNE=0 and in deterministic
   // mode, where every plan is the heuristic's top-1)
-  static const bool no_lt = ob_env_flag("OB_NO_BLASLT", false);
-  if (!no_lt) {
+  if (!no_blaslt()) {
     std::vector<ob_lt_shape> shapes;
     ob_layer_lt_list(d, l->p_resid > 0.f, &shapes);
     for (const ob_lt_shape& s : shapes)
       if (ob_lt_tune_shape(s)) return 1;
   }
   g_layers_created++;
-  *out = l;
+  *out = guard.release();
   return 0;
 }
 
@@ -555,7 +456,7 @@ extern "C" int ob_layer_create_ex(const ob_layer_desc* d,
 }
 
 extern "C" int ob_layer_uses_flash(ob_layer_t l) {
-  return l && l->flash ? 1 : 0;
+  return l && l->plan.flash ? 1 : 0;
 }
 
 extern "C" int ob_layer_set_training(ob_layer_t l, int on) {
@@ -601,31 +502,31 @@ extern "C" int ob_layer_refresh_weights(ob_layer_t l, void* stream) {
   if (!l->params) return ob_fail("refresh: params not bound");
   const int64_t H = l->d.n_embd, V = l->d.vocab_size;
   const float* p = l->params;
-  __bf16* sh = l->shadows;
   switch (l->d.kind) {
     case OB_KIND_EMBED:
       return 0;  // embedding reads the fp32 master directly
     case OB_KIND_BLOCK: {
       const BlockParams bp = block_params(H);
-      if (ob_f32_to_bf16(p + bp.w_qkv, sh + l->sh_qkv, 3 * H * H, stream) ||
-          ob_f32_to_bf16_t_ld(p + bp.w_qkv, sh + l->sh_qkv_t, H, 3 * H, H,
+      if (ob_f32_to_bf16(p + bp.w_qkv, shadow(l, SH_QKV), 3 * H * H, stream) ||
+          ob_f32_to_bf16_t_ld(p + bp.w_qkv, shadow(l, SH_QKV_T), H, 3 * H, H,
                               stream) ||
-          ob_f32_to_bf16(p + bp.w_attnproj, sh + l->sh_ap, H * H, stream) ||
-          ob_f32_to_bf16_t_ld(p + bp.w_attnproj, sh + l->sh_ap_t, H, H, H,
+          ob_f32_to_bf16(p + bp.w_attnproj, shadow(l, SH_AP), H * H, stream) ||
+          ob_f32_to_bf16_t_ld(p + bp.w_attnproj, shadow(l, SH_AP_T), H, H, H,
                               stream) ||
-          ob_f32_to_bf16(p + bp.w_fc, sh + l->sh_fc, 4 * H * H, stream) ||
-          ob_f32_to_bf16_t_ld(p + bp.w_fc, sh + l->sh_fc_t, H, 4 * H, H,
+          ob_f32_to_bf16(p + bp.w_fc, shadow(l, SH_FC), 4 * H * H, stream) ||
+          ob_f32_to_bf16_t_ld(p + bp.w_fc, shadow(l, SH_FC_T), H, 4 * H, H,
                               stream) ||
-          ob_f32_to_bf16(p + bp.w_mlpproj, sh + l->sh_mp, 4 * H * H, stream) ||
-          ob_f32_to_bf16_t_ld(p + bp.w_mlpproj, sh + l->sh_mp_t, 4 * H, H,
+          ob_f32_to_bf16(p + bp.w_mlpproj, shadow(l, SH_MP), 4 * H * H,
+                         stream) ||
+          ob_f32_to_bf16_t_ld(p + bp.w_mlpproj, shadow(l, SH_MP_T), 4 * H, H,
                               4 * H, stream))
         return 1;
       return 0;
     }
     case OB_KIND_FINAL:
-      if (ob_f32_to_bf16(p + 2 * H, sh + l->sh_lm, V * H, stream) ||
-          ob_f32_to_bf16_t_ld(p + 2 * H, sh + l->sh_lm_t, V, H, l->v_pad,
-                              stream))
+      if (ob_f32_to_bf16(p + 2 * H, shadow(l, SH_LM), V * H, stream) ||
+          ob_f32_to_bf16_t_ld(p + 2 * H, shadow(l, SH_LM_T), V, H,
+                              l->plan.v_pad, stream))
         return 1;
       return 0;
   }
@@ -641,8 +542,7 @@ static int gemm(int tA, int tB, int64_t M, int64_t N, int64_t K, float alpha,
                 int atomic, int splitk, void* stream) {
   // plain (unbatched, no fused epilogue) fp32 GEMMs to hipBLASLt —
   // covers the dW family too (it accumulates through beta=1)
-  static const bool no_lt = ob_env_flag("OB_NO_BLASLT", false);
-  if (!no_lt && !bias && !R && !atomic && splitk <= 1 && n1 == 1 &&
+  if (!no_blaslt() && !bias && !R && !atomic && splitk <= 1 && n1 == 1 &&
       n2 == 1 && M * N >= 512 * 512) {
     const int r = ob_gemm_lt_f32(tA, tB, M, N, K, alpha, A, lda, B, ldb,
                                  beta, C, ldc, stream);
@@ -670,8 +570,7 @@ static int gemm_dx_splitk(int tB, int64_t M, int64_t N, int64_t K,
                           float alpha, const float* A, int64_t lda,
                           const float* B, int64_t ldb, float* C, int64_t ldc,
                           void* stream) {
-  static const bool no_lt = ob_env_flag("OB_NO_BLASLT", false);
-  if (!no_lt) {
+  if (!no_blaslt()) {
     const int r = ob_gemm_lt_f32(0, tB, M, N, K, alpha, A, lda, B, ldb, 0.f,
                                  C, ldc, stream);
     if (r >= 0) return r;
@@ -697,77 +596,67 @@ static int block_forward(ob_layer* l, int slot, const float* in, float* out,
   const int64_t Sq = l->d.seq_len, H = l->d.n_embd, nh = l->d.n_head;
   const int64_t B = l->B, BS = B * Sq;
   const int64_t hd = H / nh;
-  float* st = l->stash + (int64_t)slot * l->slot_stride;
   const float* p = l->params;
+  const BlockStash<float> s(l, slot);
   const BlockParams bp = block_params(H);
   const bool dA = l->slot_drop[slot] && l->p_attn > 0.f;
   const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;
 
-  float* x = st + l->o_x;
-  OB_HIP(hipMemcpyAsync(x, in, BS * H * sizeof(float), hipMemcpyDeviceToDevice,
-                        S(stream)));
-  float* ln1 = st + l->o_ln1;
-  if (ob_layernorm_fwd_f32(x, p + bp.ln1_w, p + bp.ln1_b, ln1,
-                           st + l->o_mean1, st + l->o_rstd1, BS, H, 1e-5f,
-                           stream))
+  OB_HIP(hipMemcpyAsync(s.x, in, BS * H * sizeof(float),
+                        hipMemcpyDeviceToDevice, S(stream)));
+  if (ob_layernorm_fwd_f32(s.x, p + bp.ln1_w, p + bp.ln1_b, s.ln1, s.mean1,
+                           s.rstd1, BS, H, 1e-5f, stream))
     return 1;
-  float* qkv = st + l->o_qkv;
-  if (gemm(0, 0, BS, 3 * H, H, 1.f, ln1, H, 0, 0, p + bp.w_qkv, 3 * H, 0, 0,
-           0.f, qkv, 3 * H, 0, 0, 1, 1, p + bp.b_qkv, nullptr, 0, 1, stream))
+  if (gemm(0, 0, BS, 3 * H, H, 1.f, s.ln1, H, 0, 0, p + bp.w_qkv, 3 * H, 0, 0,
+           0.f, s.qkv, 3 * H, 0, 0, 1, 1, p + bp.b_qkv, nullptr, 0, 1, stream))
     return 1;
   // scores: P[b,h] = Q @ K^T ; Q/K are strided slices of qkv
-  float* P = st + l->o_p;
   if (gemm(0, 1, Sq, Sq, hd, 1.f,
-           qkv, 3 * H, Sq * 3 * H, hd,            // Q slice
-           qkv + H, 3 * H, Sq * 3 * H, hd,        // K slice (stored [S,hd])
-           0.f, P, Sq, nh * Sq * Sq, Sq * Sq, B, nh, nullptr, nullptr, 0, 1,
+           s.qkv, 3 * H, Sq * 3 * H, hd,            // Q slice
+           s.qkv + H, 3 * H, Sq * 3 * H, hd,        // K slice (stored [S,hd])
+           0.f, s.P, Sq, nh * Sq * Sq, Sq * Sq, B, nh, nullptr, nullptr, 0, 1,
            stream))
     return 1;
-  if (ob_softmax_causal_fwd_f32(P, B * nh, Sq, 1.f / sqrtf((float)hd), stream))
+  if (ob_softmax_causal_fwd_f32(s.P, B * nh, Sq, 1.f / sqrtf((float)hd),
+                                stream))
     return 1;
   // attention dropout: the stash keeps the undropped P (softmax backward
   // needs it at dropped positions); the PV GEMM reads Pd = drop(P) from the
   // forward-only workspace
-  const float* Pv = P;
+  const float* Pv = s.P;
   if (dA) {
-    if (ob_drop_scale(drop_key(l, slot, OB_DROP_ATTN, l->p_attn), 0, P,
-                      g_ws.pd_f, B * nh * Sq * Sq, stream))
+    if (ob_drop_scale(drop_key(l, slot, OB_DROP_ATTN, l->p_attn), 0, s.P,
+                      ws<float>(WS_PD_FWD), B * nh * Sq * Sq, stream))
       return 1;
-    Pv = g_ws.pd_f;
+    Pv = ws<float>(WS_PD_FWD);
   }
   // attn_merged[b,:,h*hd:(h+1)*hd] = Pd[b,h] @ V[b,h]
-  float* am = st + l->o_attnm;
-  if (gemm(0, 0, Sq, hd, Sq, 1.f, Pv, Sq, nh * Sq * Sq, Sq * Sq, qkv + 2 * H,
-           3 * H, Sq * 3 * H, hd, 0.f, am, H, Sq * H, hd, B, nh, nullptr,
+  if (gemm(0, 0, Sq, hd, Sq, 1.f, Pv, Sq, nh * Sq * Sq, Sq * Sq, s.qkv + 2 * H,
+           3 * H, Sq * 3 * H, hd, 0.f, s.am, H, Sq * H, hd, B, nh, nullptr,
            nullptr, 0, 1, stream))
     return 1;
   // h_mid = attn_merged @ w_attnproj + b + x (residual)
-  float* hmid = st + l->o_hmid;
-  if (gemm(0, 0, BS, H, H, 1.f, am, H, 0, 0, p + bp.w_attnproj, H, 0, 0, 0.f,
-           hmid, H, 0, 0, 1, 1, p + bp.b_attnproj, dR ? nullptr : x, 0, 1,
+  if (gemm(0, 0, BS, H, H, 1.f, s.am, H, 0, 0, p + bp.w_attnproj, H, 0, 0, 0.f,
+           s.hmid, H, 0, 0, 1, 1, p + bp.b_attnproj, dR ? nullptr : s.x, 0, 1,
            stream))
     return 1;
   // residual dropout: the GEMM wrote the biased projection only
   if (dR && ob_drop_add(drop_key(l, slot, OB_DROP_RESID_ATTN, l->p_resid), 0,
-                        hmid, x, hmid, BS * H, stream))
+                        s.hmid, s.x, s.hmid, BS * H, stream))
     return 1;
-  float* ln2 = st + l->o_ln2;
-  if (ob_layernorm_fwd_f32(hmid, p + bp.ln2_w, p + bp.ln2_b, ln2,
-                           st + l->o_mean2, st + l->o_rstd2, BS, H, 1e-5f,
-                           stream))
+  if (ob_layernorm_fwd_f32(s.hmid, p + bp.ln2_w, p + bp.ln2_b, s.ln2, s.mean2,
+                           s.rstd2, BS, H, 1e-5f, stream))
     return 1;
-  float* u = st + l->o_u;
-  if (gemm(0, 0, BS, 4 * H, H, 1.f, ln2, H, 0, 0, p + bp.w_fc, 4 * H, 0, 0,
-           0.f, u, 4 * H, 0, 0, 1, 1, p + bp.b_fc, nullptr, 0, 1, stream))
+  if (gemm(0, 0, BS, 4 * H, H, 1.f, s.ln2, H, 0, 0, p + bp.w_fc, 4 * H, 0, 0,
+           0.f, s.u, 4 * H, 0, 0, 1, 1, p + bp.b_fc, nullptr, 0, 1, stream))
     return 1;
-  float* gact = st + l->o_g;
-  if (ob_gelu_fwd_f32(u, gact, BS * 4 * H, stream)) return 1;
-  if (gemm(0, 0, BS, H, 4 * H, 1.f, gact, 4 * H, 0, 0, p + bp.w_mlpproj, H, 0,
-           0, 0.f, out, H, 0, 0, 1, 1, p + bp.b_mlpproj, dR ? nullptr : hmid,
+  if (ob_gelu_fwd_f32(s.u, s.gact, BS * 4 * H, stream)) return 1;
+  if (gemm(0, 0, BS, H, 4 * H, 1.f, s.gact, 4 * H, 0, 0, p + bp.w_mlpproj, H, 0,
+           0, 0.f, out, H, 0, 0, 1, 1, p + bp.b_mlpproj, dR ? nullptr : s.hmid,
            0, 1, stream))
     return 1;
   if (dR && ob_drop_add(drop_key(l, slot, OB_DROP_RESID_MLP, l->p_resid), 0,
-                        out, hmid, out, BS * H, stream))
+                        out, s.hmid, out, BS * H, stream))
     return 1;
   return 0;
 }
@@ -776,29 +665,23 @@ static int final_forward(ob_layer* l, int slot, const float* in, float* out,
                          const int64_t* labels, void* stream) {
   const int64_t Sq = l->d.seq_len, H = l->d.n_embd, V = l->d.vocab_size;
   const int64_t B = l->B, BS = B * Sq;
-  float* st = l->stash + (int64_t)slot * l->slot_stride;
   const float* p = l->params;
+  const FinalStash<float> s(l, slot);
   if (!labels) return ob_fail("final_forward: labels required");
 
-  float* x = st + l->o_x;
-  OB_HIP(hipMemcpyAsync(x, in, BS * H * sizeof(float), hipMemcpyDeviceToDevice,
-                        S(stream)));
-  int64_t* labs = l->ids + (int64_t)slot * (int64_t)l->d.max_batch * Sq;
-  OB_HIP(hipMemcpyAsync(labs, labels, BS * sizeof(int64_t),
+  OB_HIP(hipMemcpyAsync(s.x, in, BS * H * sizeof(float),
                         hipMemcpyDeviceToDevice, S(stream)));
-  float* lnf = st + l->o_ln1;
-  if (ob_layernorm_fwd_f32(x, p + 0, p + H, lnf, st + l->o_mean1,
-                           st + l->o_rstd1, BS, H, 1e-5f, stream))
+  OB_HIP(hipMemcpyAsync(s.labs, labels, BS * sizeof(int64_t),
+                        hipMemcpyDeviceToDevice, S(stream)));
+  if (ob_layernorm_fwd_f32(s.x, p + 0, p + H, s.lnf, s.mean, s.rstd, BS, H,
+                           1e-5f, stream))
     return 1;
-  float* logits = st + l->o_logits;
   // logits = ln_out @ w_lm^T   (w_lm stored [V,H])
-  if (gemm(0, 1, BS, V, H, 1.f, lnf, H, 0, 0, p + 2 * H, H, 0, 0, 0.f, logits,
-           V, 0, 0, 1, 1, nullptr, nullptr, 0, 1, stream))
+  if (gemm(0, 1, BS, V, H, 1.f, s.lnf, H, 0, 0, p + 2 * H, H, 0, 0, 0.f,
+           s.logits, V, 0, 0, 1, 1, nullptr, nullptr, 0, 1, stream))
     return 1;
   OB_HIP(hipMemsetAsync(out, 0, sizeof(float), S(stream)));
-  if (ob_ce_fwd_f32(logits, labs, st + l->o_lse, out, B, Sq, V, stream))
-    return 1;
-  return 0;
+  return ob_ce_fwd_f32(s.logits, s.labs, s.lse, out, B, Sq, V, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -869,7 +752,7 @@ static void ob_layer_lt_list(const ob_layer_desc* d, bool resid_drop,
     block_gemms(H, BS, true, g);
     n = LG_BLOCK_N;
   } else if (d->kind == OB_KIND_FINAL) {
-    final_gemms(H, V, v_pad_of(V), BS, g);
+    final_gemms(H, V, ob_v_pad(V), BS, g);
     n = LG_FINAL_N;
   }
   for (int i = 0; i < n; i++)
@@ -925,14 +808,12 @@ static ob_bf16_gemm attn_gemm(int tA, int tB, int64_t M, int64_t N, int64_t K,
 // so the GEMM runs on the fast NT glds path instead of the
 // transpose-staged TN case (~150 TF measured there).
 static int dw_bf16_ws(const ob_lt_shape& s, const __bf16* act,
-                      const __bf16* dY, float* gout, float* w1, float* w2,
-                      void* stream) {
+                      const __bf16* dY, float* gout, void* stream) {
   const int64_t actw = s.M, dyw = s.N, BS = s.K, ldc = s.ldc;
   // direct TN via hipBLASLt with beta=1 accumulation into the fp32 flat
   // grads: no transpose materialization, no atomics (measured 694 TF on
   // the fc dW shape vs 436 for transpose + atomic NT)
-  static const bool no_lt = ob_env_flag("OB_NO_BLASLT", false);
-  if (!no_lt) {
+  if (!no_blaslt()) {
     const int r = ob_gemm_lt(s.tA, s.tB, s.M, s.N, s.K, 1.f, act, s.lda, dY,
                              s.ldb, 1.f, gout, s.ldc, s.c_f32, stream);
     if (r >= 0) return r;
@@ -948,8 +829,8 @@ static int dw_bf16_ws(const ob_lt_shape& s, const __bf16* act,
     g.A = act, g.lda = actw, g.B = dY, g.ldb = dyw;
     return ob_gemm_bf16_run(g);
   }
-  __bf16* XT = (__bf16*)w1;
-  __bf16* DYT = (__bf16*)w2;
+  __bf16* XT = ws<__bf16>(WS_DW_A);
+  __bf16* DYT = ws<__bf16>(WS_DW_B);
   if (ob_transpose_bf16(act, XT, BS, actw, stream)) return 1;
   if (ob_transpose_bf16(dY, DYT, BS, dyw, stream)) return 1;
   g.A = XT, g.lda = BS, g.B = DYT, g.ldb = BS;
@@ -961,9 +842,8 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   const int64_t Sq = l->d.seq_len, H = l->d.n_embd, nh = l->d.n_head;
   const int64_t B = l->B, BS = B * Sq;
   const int64_t hd = H / nh;
-  float* st = l->stash + (int64_t)slot * l->slot_stride;
   const float* p = l->params;
-  const __bf16* sh = l->shadows;
+  const BlockStash<__bf16> s(l, slot);
   const BlockParams bp = block_params(H);
   const bool dA = l->slot_drop[slot] && l->p_attn > 0.f;
   const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;
@@ -971,109 +851,98 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   block_gemms(H, BS, !dR, lg);
 
   // ln1 reads the input once and also writes its stash copy x
-  __bf16* x = (__bf16*)(st + l->o_x);
-  __bf16* ln1 = (__bf16*)(st + l->o_ln1);
   if (OB_PROF(OB_PF_LN, stream,
-              ob_layernorm_fwd_copy_bf16(in, p + bp.ln1_w, p + bp.ln1_b, ln1,
-                                         x, st + l->o_mean1, st + l->o_rstd1,
-                                         BS, H, 1e-5f, stream)))
+              ob_layernorm_fwd_copy_bf16(in, p + bp.ln1_w, p + bp.ln1_b, s.ln1,
+                                         s.x, s.mean1, s.rstd1, BS, H, 1e-5f,
+                                         stream)))
     return 1;
-  __bf16* qkv = (__bf16*)(st + l->o_qkv);
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
-              linear_bf(lg[LG_QKV], ln1, sh + l->sh_qkv_t, p + bp.b_qkv,
-                        nullptr, qkv, stream)))
+              linear_bf(lg[LG_QKV], s.ln1, shadow(l, SH_QKV_T), p + bp.b_qkv,
+                        nullptr, s.qkv, stream)))
     return 1;
-  __bf16* am = (__bf16*)(st + l->o_attnm);
-  if (l->flash && flash_tr()) {
+  if (l->plan.flash && flash_tr()) {
     // the fused kernel writes O and the per-row LSE (stored where the
     // materialized-P path keeps P)
-    float* lseP = st + l->o_p;
     if (dA) {
       // attention dropout inside the kernel: masks of this slot's tick
       if (OB_PROF(OB_PF_FLASH_FWD, stream,
-                  ob_flash_fwd_nt_drop_bf16(qkv, am, lseP, B, Sq, H, nh,
+                  ob_flash_fwd_nt_drop_bf16(s.qkv, s.am, s.lseP, B, Sq, H, nh,
                                             1.f / sqrtf((float)hd), l->seed,
                                             l->layer_id, l->slot_tick[slot],
                                             l->p_attn, stream)))
         return 1;
     } else if (OB_PROF(OB_PF_FLASH_FWD, stream,
-                       ob_flash_fwd_nt_bf16(qkv, am, lseP, B, Sq, H, nh,
+                       ob_flash_fwd_nt_bf16(s.qkv, s.am, s.lseP, B, Sq, H, nh,
                                             1.f / sqrtf((float)hd), stream)))
       return 1;
-  } else if (l->flash) {
+  } else if (l->plan.flash) {
     // OB_FLASH_TR=0: V^T materialization (workspace, transient within this
     // call) feeding the kernel that takes a transposed V
-    __bf16* VTw = (__bf16*)g_ws.t2;
+    __bf16* VTw = ws<__bf16>(WS_FLASH_VT);
     if (OB_PROF(OB_PF_FLASH_FWD, stream,
-                ob_transpose_bf16_b(qkv + 2 * H, VTw, Sq, 64, Sq * 3 * H, 64,
+                ob_transpose_bf16_b(s.qkv + 2 * H, VTw, Sq, 64, Sq * 3 * H, 64,
                                     3 * H, B, nh, stream)))
       return 1;
-    float* lseP = st + l->o_p;
     if (OB_PROF(OB_PF_FLASH_FWD, stream,
-                ob_flash_fwd_bf16(qkv, VTw, am, lseP, B, Sq, H, nh,
+                ob_flash_fwd_bf16(s.qkv, VTw, s.am, s.lseP, B, Sq, H, nh,
                                   1.f / sqrtf((float)hd), stream)))
       return 1;
   } else {
-    __bf16* P = (__bf16*)(st + l->o_p);
     ob_bf16_gemm qk = attn_gemm(0, 1, Sq, Sq, hd, 1.f, B, nh, stream);
-    qk.A = qkv, qk.lda = 3 * H, qk.sA1 = Sq * 3 * H, qk.sA2 = hd;
-    qk.B = qkv + H, qk.ldb = 3 * H, qk.sB1 = Sq * 3 * H, qk.sB2 = hd;
-    qk.C = P, qk.ldc = Sq, qk.sC1 = nh * Sq * Sq, qk.sC2 = Sq * Sq;
+    qk.A = s.qkv, qk.lda = 3 * H, qk.sA1 = Sq * 3 * H, qk.sA2 = hd;
+    qk.B = s.qkv + H, qk.ldb = 3 * H, qk.sB1 = Sq * 3 * H, qk.sB2 = hd;
+    qk.C = s.P, qk.ldc = Sq, qk.sC1 = nh * Sq * Sq, qk.sC2 = Sq * Sq;
     if (OB_PROF(OB_PF_ATTN_MAT, stream, ob_gemm_bf16_run(qk))) return 1;
     if (OB_PROF(OB_PF_ATTN_MAT, stream,
-                ob_softmax_causal_fwd_bf16(P, B * nh, Sq,
+                ob_softmax_causal_fwd_bf16(s.P, B * nh, Sq,
                                            1.f / sqrtf((float)hd), stream)))
       return 1;
     // attention dropout: stash keeps P, the PV GEMM reads Pd = drop(P) from
     // the forward-only workspace (only a non-flash layer gets here with dA)
-    const __bf16* Pv = P;
+    const __bf16* Pv = s.P;
     if (dA) {
       if (OB_PROF(OB_PF_ELEM, stream,
                   ob_drop_scale(drop_key(l, slot, OB_DROP_ATTN, l->p_attn), 1,
-                                P, g_ws.pd_f, B * nh * Sq * Sq, stream)))
+                                s.P, ws<__bf16>(WS_PD_FWD), B * nh * Sq * Sq,
+                                stream)))
         return 1;
-      Pv = (const __bf16*)g_ws.pd_f;
+      Pv = ws<__bf16>(WS_PD_FWD);
     }
     ob_bf16_gemm pv = attn_gemm(0, 0, Sq, hd, Sq, 1.f, B, nh, stream);
     pv.A = Pv, pv.lda = Sq, pv.sA1 = nh * Sq * Sq, pv.sA2 = Sq * Sq;
-    pv.B = qkv + 2 * H, pv.ldb = 3 * H, pv.sB1 = Sq * 3 * H, pv.sB2 = hd;
-    pv.C = am, pv.ldc = H, pv.sC1 = Sq * H, pv.sC2 = hd;
+    pv.B = s.qkv + 2 * H, pv.ldb = 3 * H, pv.sB1 = Sq * 3 * H, pv.sB2 = hd;
+    pv.C = s.am, pv.ldc = H, pv.sC1 = Sq * H, pv.sC2 = hd;
     if (OB_PROF(OB_PF_ATTN_MAT, stream, ob_gemm_bf16_run(pv))) return 1;
   }
-  __bf16* hmid = (__bf16*)(st + l->o_hmid);
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
-              linear_bf(lg[LG_AP], am, sh + l->sh_ap_t, p + bp.b_attnproj,
-                        dR ? nullptr : x, hmid, stream)))
+              linear_bf(lg[LG_AP], s.am, shadow(l, SH_AP_T), p + bp.b_attnproj,
+                        dR ? nullptr : s.x, s.hmid, stream)))
     return 1;
   // residual dropout: the GEMM wrote the biased projection only
   if (dR &&
       OB_PROF(OB_PF_ELEM, stream,
               ob_drop_add(drop_key(l, slot, OB_DROP_RESID_ATTN, l->p_resid), 1,
-                          hmid, x, hmid, BS * H, stream)))
+                          s.hmid, s.x, s.hmid, BS * H, stream)))
     return 1;
-  __bf16* ln2 = (__bf16*)(st + l->o_ln2);
   if (OB_PROF(OB_PF_LN, stream,
-              ob_layernorm_fwd_bf16(hmid, p + bp.ln2_w, p + bp.ln2_b, ln2,
-                                    st + l->o_mean2, st + l->o_rstd2, BS, H,
-                                    1e-5f, stream)))
+              ob_layernorm_fwd_bf16(s.hmid, p + bp.ln2_w, p + bp.ln2_b, s.ln2,
+                                    s.mean2, s.rstd2, BS, H, 1e-5f, stream)))
     return 1;
-  __bf16* u = (__bf16*)(st + l->o_u);
   if (OB_PROF(OB_PF_FC_FWD, stream,
-              linear_bf(lg[LG_FC], ln2, sh + l->sh_fc_t, p + bp.b_fc,
-                        nullptr, u, stream)))
+              linear_bf(lg[LG_FC], s.ln2, shadow(l, SH_FC_T), p + bp.b_fc,
+                        nullptr, s.u, stream)))
     return 1;
-  __bf16* gact = (__bf16*)(st + l->o_g);
   if (OB_PROF(OB_PF_ELEM, stream,
-              ob_gelu_fwd_bf16(u, gact, BS * 4 * H, stream)))
+              ob_gelu_fwd_bf16(s.u, s.gact, BS * 4 * H, stream)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
-              linear_bf(lg[LG_MP], gact, sh + l->sh_mp_t,
-                        p + bp.b_mlpproj, dR ? nullptr : hmid, out, stream)))
+              linear_bf(lg[LG_MP], s.gact, shadow(l, SH_MP_T),
+                        p + bp.b_mlpproj, dR ? nullptr : s.hmid, out, stream)))
     return 1;
   if (dR &&
       OB_PROF(OB_PF_ELEM, stream,
               ob_drop_add(drop_key(l, slot, OB_DROP_RESID_MLP, l->p_resid), 1,
-                          out, hmid, out, BS * H, stream)))
+                          out, s.hmid, out, BS * H, stream)))
     return 1;
   return 0;
 }
@@ -1083,37 +952,29 @@ static int final_forward_bf16(ob_layer* l, int slot, const __bf16* in,
                               void* stream) {
   const int64_t Sq = l->d.seq_len, H = l->d.n_embd, V = l->d.vocab_size;
   const int64_t B = l->B, BS = B * Sq;
-  float* st = l->stash + (int64_t)slot * l->slot_stride;
   const float* p = l->params;
+  const FinalStash<__bf16> s(l, slot);
   if (!labels) return ob_fail("final_forward_bf16: labels required");
   ob_lt_shape lg[LG_FINAL_N];
-  final_gemms(H, V, l->v_pad, BS, lg);
+  final_gemms(H, V, l->plan.v_pad, BS, lg);
 
-  __bf16* x = (__bf16*)(st + l->o_x);
-  int64_t* labs = l->ids + (int64_t)slot * (int64_t)l->d.max_batch * Sq;
-  OB_HIP(hipMemcpyAsync(labs, labels, BS * sizeof(int64_t),
+  OB_HIP(hipMemcpyAsync(s.labs, labels, BS * sizeof(int64_t),
                         hipMemcpyDeviceToDevice, S(stream)));
-  __bf16* lnf = (__bf16*)(st + l->o_ln1);
   if (OB_PROF(OB_PF_LN, stream,
-              ob_layernorm_fwd_copy_bf16(in, p + 0, p + H, lnf, x,
-                                         st + l->o_mean1, st + l->o_rstd1,
-                                         BS, H, 1e-5f, stream)))
+              ob_layernorm_fwd_copy_bf16(in, p + 0, p + H, s.lnf, s.x, s.mean,
+                                         s.rstd, BS, H, 1e-5f, stream)))
     return 1;
-  __bf16* logits = (__bf16*)(st + l->o_logits);
   // N = v_pad (zero-padded shadow rows -> padded logits are exactly 0)
   if (OB_PROF(OB_PF_GEMM_FWD, stream,
-              linear_bf(lg[LG_LM], lnf, l->shadows + l->sh_lm, nullptr,
-                        nullptr, logits, stream)))
+              linear_bf(lg[LG_LM], s.lnf, shadow(l, SH_LM), nullptr, nullptr,
+                        s.logits, stream)))
     return 1;
   OB_HIP(hipMemsetAsync(out, 0, sizeof(float), S(stream)));
   // deterministic mode: the loss through the forward stream's slab
-  if (OB_PROF(OB_PF_CE, stream,
-              ob_ce_fwd_ws(logits, labs, st + l->o_lse, out, B, Sq, V,
-                           l->v_pad,
-                           ob_deterministic() ? g_ws.det_fwd : nullptr,
-                           stream)))
-    return 1;
-  return 0;
+  float* const wsf = ob_deterministic() ? ws<float>(WS_DET_FWD) : nullptr;
+  return OB_PROF(OB_PF_CE, stream,
+                 ob_ce_fwd_ws(s.logits, s.labs, s.lse, out, B, Sq, V,
+                              l->plan.v_pad, wsf, stream));
 }
 
 static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
@@ -1122,27 +983,11 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   const int64_t B = l->B, BS = B * Sq;
   const int64_t hd = H / nh;
   const float scale = 1.f / sqrtf((float)hd);
-  float* st = l->stash + (int64_t)slot * l->slot_stride;
   const float* p = l->params;
+  const BlockStash<__bf16> s(l, slot);
+  const BwdWs<__bf16> w(l);
   float* g = l->grads;
-  const __bf16* sh = l->shadows;
   const BlockParams bp = block_params(H);
-
-  __bf16* x = (__bf16*)(st + l->o_x);
-  __bf16* ln1 = (__bf16*)(st + l->o_ln1);
-  __bf16* qkv = (__bf16*)(st + l->o_qkv);
-  __bf16* P = (__bf16*)(st + l->o_p);
-  __bf16* am = (__bf16*)(st + l->o_attnm);
-  __bf16* hmid = (__bf16*)(st + l->o_hmid);
-  __bf16* ln2 = (__bf16*)(st + l->o_ln2);
-  __bf16* u = (__bf16*)(st + l->o_u);
-  __bf16* gact = (__bf16*)(st + l->o_g);
-
-  __bf16* DY4 = (__bf16*)g_ws.b4h;
-  __bf16* DLN = (__bf16*)g_ws.bsh1;
-  __bf16* DATT = (__bf16*)g_ws.bsh2;
-  __bf16* DQKV = (__bf16*)g_ws.dqkv;
-  __bf16* DP = (__bf16*)g_ws.dp;
   // the masks this slot's forward drew, regenerated from its tick
   const bool dA = l->slot_drop[slot] && l->p_attn > 0.f;
   const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;
@@ -1151,7 +996,7 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   // deterministic mode: the same calls, same places, same streams, with
   // the stream's slab (null: the atomic kernels)
   const bool det = ob_deterministic() != 0;
-  float* const wsm = det ? g_ws.det_main : nullptr;
+  float* const wsm = det ? ws<float>(WS_DET_MAIN) : nullptr;
 
   // The dW family (transposes + atomic GEMMs + the qkv bias colsum) has
   // no consumer inside this call and no effect on the dX chain (the other
@@ -1171,40 +1016,38 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     if (OB_PROF(OB_PF_ELEM, stream,
                 ob_drop_scale_colsum(
                     drop_key(l, slot, OB_DROP_RESID_MLP, l->p_resid), 1, dout,
-                    g_ws.dm2, g + bp.b_mlpproj, BS, H, stream, wsm)))
+                    w.dm2, g + bp.b_mlpproj, BS, H, stream, wsm)))
       return 1;
-    dmlp = (const __bf16*)g_ws.dm2;
+    dmlp = w.dm2;
     OB_SIDE_FENCE(S(stream), g_side.stream);  // dm2 ready
   }
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              linear_bf(lg[LG_DX_MP], dmlp, sh + l->sh_mp, nullptr, nullptr,
-                        DY4, stream)))
+              linear_bf(lg[LG_DX_MP], dmlp, shadow(l, SH_MP), nullptr, nullptr,
+                        w.DY4, stream)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DW, side,
-              dw_bf16_ws(lg[LG_DW_MP], gact, dmlp, g + bp.w_mlpproj,
-                         g_ws.s1, g_ws.s2, side)))
+              dw_bf16_ws(lg[LG_DW_MP], s.gact, dmlp, g + bp.w_mlpproj, side)))
     return 1;
   // gelu backward also sums its output columns into the b_fc grad
   if (OB_PROF(OB_PF_ELEM, stream,
-              ob_gelu_bwd_colsum_ws(u, DY4, DY4, g + bp.b_fc, BS, 4 * H, wsm,
-                                    stream)))
+              ob_gelu_bwd_colsum_ws(s.u, w.DY4, w.DY4, g + bp.b_fc, BS, 4 * H,
+                                    wsm, stream)))
     return 1;
   OB_SIDE_FENCE(S(stream), g_side.stream);  // DY4 post-gelu
   if (OB_PROF(OB_PF_GEMM_DW, side,
-              dw_bf16_ws(lg[LG_DW_FC], ln2, DY4, g + bp.w_fc, g_ws.s1,
-                         g_ws.s2, side)))
+              dw_bf16_ws(lg[LG_DW_FC], s.ln2, w.DY4, g + bp.w_fc, side)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              linear_bf(lg[LG_DX_FC], DY4, sh + l->sh_fc, nullptr, nullptr,
-                        DLN, stream)))
+              linear_bf(lg[LG_DX_FC], w.DY4, shadow(l, SH_FC), nullptr,
+                        nullptr, w.DLN, stream)))
     return 1;
   // ln2 backward takes the residual straight from dout (din = dout + v,
   // no entry copy) and sums both streams it holds in registers: dout
   // columns -> b_mlpproj grad, din columns -> b_attnproj grad
   if (OB_PROF(OB_PF_LN, stream,
-              ob_layernorm_bwd_res_ws(hmid, p + bp.ln2_w, st + l->o_mean2,
-                                      st + l->o_rstd2, DLN, dout, din,
-                                      g + bp.ln2_w, g + bp.ln2_b,
+              ob_layernorm_bwd_res_ws(s.hmid, p + bp.ln2_w, s.mean2, s.rstd2,
+                                      w.DLN, dout, din, g + bp.ln2_w,
+                                      g + bp.ln2_b,
                                       dR ? nullptr : g + bp.b_mlpproj,
                                       dR ? nullptr : g + bp.b_attnproj,
                                       BS, H, wsm, stream)))
@@ -1215,131 +1058,120 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     if (OB_PROF(OB_PF_ELEM, stream,
                 ob_drop_scale_colsum(
                     drop_key(l, slot, OB_DROP_RESID_ATTN, l->p_resid), 1, din,
-                    g_ws.dm1, g + bp.b_attnproj, BS, H, stream, wsm)))
+                    w.dm1, g + bp.b_attnproj, BS, H, stream, wsm)))
       return 1;
-    dap = (const __bf16*)g_ws.dm1;
+    dap = w.dm1;
   }
   OB_SIDE_FENCE(S(stream), g_side.stream);  // din post-ln2-bwd (dm1 ready)
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              linear_bf(lg[LG_DX_AP], dap, sh + l->sh_ap, nullptr, nullptr, DATT,
-                        stream)))
+              linear_bf(lg[LG_DX_AP], dap, shadow(l, SH_AP), nullptr, nullptr,
+                        w.DATT, stream)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DW, side,
-              dw_bf16_ws(lg[LG_DW_AP], am, dap, g + bp.w_attnproj, g_ws.s1,
-                         g_ws.s2, side)))
+              dw_bf16_ws(lg[LG_DW_AP], s.am, dap, g + bp.w_attnproj, side)))
     return 1;
   // din is re-updated by the final ln1 backward: the main stream must
   // not reach it before the side finished reading din
   hipEvent_t ev_din_done = side_evt();
   OB_HIP(hipEventRecord(ev_din_done, g_side.stream));
   // ---- attention core ----
-  const bool flash_nt = l->flash && flash_tr();
+  const bool flash_nt = l->plan.flash && flash_tr();
   if (flash_nt) {
-    float* Dbuf = g_ws.t1;
-    const float* lseP = st + l->o_p;
-    // the dq kernel forms D = rowsum(dO * O) into Dbuf for the dkdv kernel;
+    // the dq kernel forms D = rowsum(dO * O) into w.D for the dkdv kernel;
     // also adds the b_qkv grad (column sums of DQKV) from its accumulators
     // (deterministic mode: not asked for; the side-stream colsum below)
     float* const dbq = det ? nullptr : g + bp.b_qkv;
     if (dA) {
       // regenerates the masks the forward of this slot drew
       if (OB_PROF(OB_PF_FLASH_BWD, stream,
-                  ob_flash_bwd_nt_d_drop_bf16(qkv, am, DATT, lseP, Dbuf, DQKV,
-                                              dbq, B, Sq, H, nh,
-                                              scale, l->seed, l->layer_id,
+                  ob_flash_bwd_nt_d_drop_bf16(s.qkv, s.am, w.DATT, s.lseP, w.D,
+                                              w.DQKV, dbq, B, Sq, H, nh, scale,
+                                              l->seed, l->layer_id,
                                               l->slot_tick[slot], l->p_attn,
                                               stream)))
         return 1;
     } else if (OB_PROF(OB_PF_FLASH_BWD, stream,
-                       ob_flash_bwd_nt_d_bf16(qkv, am, DATT, lseP, Dbuf, DQKV,
-                                              dbq, B, Sq, H, nh, scale,
+                       ob_flash_bwd_nt_d_bf16(s.qkv, s.am, w.DATT, s.lseP, w.D,
+                                              w.DQKV, dbq, B, Sq, H, nh, scale,
                                               stream)))
       return 1;
-  } else if (l->flash) {
-    const int64_t BSH = BS * H;
-    __bf16* QTw = (__bf16*)g_ws.t1;
-    __bf16* KTw = QTw + BSH;
-    __bf16* dOTw = KTw + BSH;
-    float* Dbuf = g_ws.t1 + (3 * BSH + 1) / 2;
-    const float* lseP = st + l->o_p;
+  } else if (l->plan.flash) {
     if (OB_PROF(OB_PF_FLASH_BWD, stream,
-                ob_transpose_bf16_b(qkv, QTw, Sq, 64, Sq * 3 * H, 64, 3 * H,
+                ob_transpose_bf16_b(s.qkv, w.QT, Sq, 64, Sq * 3 * H, 64, 3 * H,
                                     B, nh, stream)))
       return 1;
     if (OB_PROF(OB_PF_FLASH_BWD, stream,
-                ob_transpose_bf16_b(qkv + H, KTw, Sq, 64, Sq * 3 * H, 64,
+                ob_transpose_bf16_b(s.qkv + H, w.KT, Sq, 64, Sq * 3 * H, 64,
                                     3 * H, B, nh, stream)))
       return 1;
     if (OB_PROF(OB_PF_FLASH_BWD, stream,
-                ob_transpose_bf16_b(DATT, dOTw, Sq, 64, Sq * H, 64, H, B, nh,
-                                    stream)))
+                ob_transpose_bf16_b(w.DATT, w.dOT, Sq, 64, Sq * H, 64, H, B,
+                                    nh, stream)))
       return 1;
     if (OB_PROF(OB_PF_FLASH_BWD, stream,
-                ob_flash_dsum_bf16(am, DATT, Dbuf, B, Sq, H, nh, stream)))
+                ob_flash_dsum_bf16(s.am, w.DATT, w.D, B, Sq, H, nh, stream)))
       return 1;
     if (OB_PROF(OB_PF_FLASH_BWD, stream,
-                ob_flash_bwd_bf16(qkv, QTw, KTw, dOTw, DATT, lseP, Dbuf,
-                                  DQKV, B, Sq, H, nh, scale, stream)))
+                ob_flash_bwd_bf16(s.qkv, w.QT, w.KT, w.dOT, w.DATT, s.lseP,
+                                  w.D, w.DQKV, B, Sq, H, nh, scale, stream)))
       return 1;
   } else {
     // dPd = dO V^T
     ob_bf16_gemm dp = attn_gemm(0, 1, Sq, Sq, hd, 1.f, B, nh, stream);
-    dp.A = DATT, dp.lda = H, dp.sA1 = Sq * H, dp.sA2 = hd;
-    dp.B = qkv + 2 * H, dp.ldb = 3 * H, dp.sB1 = Sq * 3 * H, dp.sB2 = hd;
-    dp.C = DP, dp.ldc = Sq, dp.sC1 = nh * Sq * Sq, dp.sC2 = Sq * Sq;
+    dp.A = w.DATT, dp.lda = H, dp.sA1 = Sq * H, dp.sA2 = hd;
+    dp.B = s.qkv + 2 * H, dp.ldb = 3 * H, dp.sB1 = Sq * 3 * H, dp.sB2 = hd;
+    dp.C = w.DP, dp.ldc = Sq, dp.sC1 = nh * Sq * Sq, dp.sC2 = Sq * Sq;
     if (OB_PROF(OB_PF_ATTN_MAT, stream, ob_gemm_bf16_run(dp))) return 1;
     // attention dropout: DP holds dPd.  Regenerate Pd for dV, mask dPd into
     // dP in place, then the softmax backward runs on the stored P.
-    const __bf16* Pv = P;
+    const __bf16* Pv = s.P;
     if (dA) {
       const ob_drop_key ka = drop_key(l, slot, OB_DROP_ATTN, l->p_attn);
       if (OB_PROF(OB_PF_ELEM, stream,
-                  ob_drop_scale(ka, 1, P, g_ws.pd_b, B * nh * Sq * Sq,
-                                stream)))
+                  ob_drop_scale(ka, 1, s.P, w.pd, B * nh * Sq * Sq, stream)))
         return 1;
       if (OB_PROF(OB_PF_ELEM, stream,
-                  ob_drop_scale(ka, 1, DP, DP, B * nh * Sq * Sq, stream)))
+                  ob_drop_scale(ka, 1, w.DP, w.DP, B * nh * Sq * Sq, stream)))
         return 1;
-      Pv = (const __bf16*)g_ws.pd_b;
+      Pv = w.pd;
     }
     if (OB_PROF(OB_PF_ATTN_MAT, stream,
-                ob_softmax_causal_bwd_bf16(P, DP, B * nh, Sq, stream)))
+                ob_softmax_causal_bwd_bf16(s.P, w.DP, B * nh, Sq, stream)))
       return 1;
     // dQ = scale dS K, dK = scale dS^T Q, dV = Pd^T dO into DQKV's thirds
     ob_bf16_gemm dq = attn_gemm(0, 0, Sq, hd, Sq, scale, B, nh, stream);
-    dq.A = DP, dq.lda = Sq, dq.sA1 = nh * Sq * Sq, dq.sA2 = Sq * Sq;
-    dq.B = qkv + H, dq.ldb = 3 * H, dq.sB1 = Sq * 3 * H, dq.sB2 = hd;
-    dq.C = DQKV, dq.ldc = 3 * H, dq.sC1 = Sq * 3 * H, dq.sC2 = hd;
+    dq.A = w.DP, dq.lda = Sq, dq.sA1 = nh * Sq * Sq, dq.sA2 = Sq * Sq;
+    dq.B = s.qkv + H, dq.ldb = 3 * H, dq.sB1 = Sq * 3 * H, dq.sB2 = hd;
+    dq.C = w.DQKV, dq.ldc = 3 * H, dq.sC1 = Sq * 3 * H, dq.sC2 = hd;
     if (OB_PROF(OB_PF_ATTN_MAT, stream, ob_gemm_bf16_run(dq))) return 1;
     ob_bf16_gemm dk = dq;
-    dk.transA = 1, dk.B = qkv, dk.C = DQKV + H;
+    dk.transA = 1, dk.B = s.qkv, dk.C = w.DQKV + H;
     if (OB_PROF(OB_PF_ATTN_MAT, stream, ob_gemm_bf16_run(dk))) return 1;
     ob_bf16_gemm dv = dk;
-    dv.alpha = 1.f, dv.A = Pv, dv.C = DQKV + 2 * H;
-    dv.B = DATT, dv.ldb = H, dv.sB1 = Sq * H, dv.sB2 = hd;
+    dv.alpha = 1.f, dv.A = Pv, dv.C = w.DQKV + 2 * H;
+    dv.B = w.DATT, dv.ldb = H, dv.sB1 = Sq * H, dv.sB2 = hd;
     if (OB_PROF(OB_PF_ATTN_MAT, stream, ob_gemm_bf16_run(dv))) return 1;
   }
   // ---- QKV projection ----
   OB_SIDE_FENCE(S(stream), g_side.stream);  // DQKV ready
   if ((!flash_nt || det) &&
       OB_PROF(OB_PF_ELEM, side,
-              ob_colsum_ws(DQKV, g + bp.b_qkv, BS, 3 * H,
-                           det ? g_ws.det_side : nullptr, side)))
+              ob_colsum_ws(w.DQKV, g + bp.b_qkv, BS, 3 * H,
+                           det ? ws<float>(WS_DET_SIDE) : nullptr, side)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DW, side,
-              dw_bf16_ws(lg[LG_DW_QKV], ln1, DQKV, g + bp.w_qkv,
-                         g_ws.s1, g_ws.s2, side)))
+              dw_bf16_ws(lg[LG_DW_QKV], s.ln1, w.DQKV, g + bp.w_qkv, side)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              linear_bf(lg[LG_DX_QKV], DQKV, sh + l->sh_qkv, nullptr, nullptr,
-                        DLN, stream)))
+              linear_bf(lg[LG_DX_QKV], w.DQKV, shadow(l, SH_QKV), nullptr,
+                        nullptr, w.DLN, stream)))
     return 1;
   // ln1 backward accumulates into din: wait for the side's din readers
   OB_HIP(hipStreamWaitEvent(S(stream), ev_din_done, 0));
   if (OB_PROF(OB_PF_LN, stream,
-              ob_layernorm_bwd_ws(x, p + bp.ln1_w, st + l->o_mean1,
-                                  st + l->o_rstd1, DLN, din, g + bp.ln1_w,
-                                  g + bp.ln1_b, BS, H, 1, wsm, stream)))
+              ob_layernorm_bwd_ws(s.x, p + bp.ln1_w, s.mean1, s.rstd1, w.DLN,
+                                  din, g + bp.ln1_w, g + bp.ln1_b, BS, H, 1,
+                                  wsm, stream)))
     return 1;
   // join: the next call reuses DY4/DQKV/din workspaces on the main stream
   OB_SIDE_FENCE(g_side.stream, S(stream));  // join
@@ -1350,21 +1182,17 @@ static int final_backward_bf16(ob_layer* l, int slot, const float* dout,
                                __bf16* din, void* stream) {
   const int64_t Sq = l->d.seq_len, H = l->d.n_embd, V = l->d.vocab_size;
   const int64_t B = l->B, BS = B * Sq;
-  float* st = l->stash + (int64_t)slot * l->slot_stride;
   const float* p = l->params;
+  const FinalStash<__bf16> s(l, slot);
+  const BwdWs<__bf16> w(l);
   float* g = l->grads;
-  __bf16* x = (__bf16*)(st + l->o_x);
-  __bf16* lnf = (__bf16*)(st + l->o_ln1);
-  __bf16* logits = (__bf16*)(st + l->o_logits);
-  int64_t* labs = l->ids + (int64_t)slot * (int64_t)l->d.max_batch * Sq;
-  __bf16* DLN = (__bf16*)g_ws.bsh1;
   ob_lt_shape lg[LG_FINAL_N];
-  final_gemms(H, V, l->v_pad, BS, lg);
+  final_gemms(H, V, l->plan.v_pad, BS, lg);
   const ob_lt_shape& dwlm = lg[LG_DW_LM];
 
   if (OB_PROF(OB_PF_CE, stream,
-              ob_ce_bwd_bf16(logits, labs, st + l->o_lse, dout, B, Sq, V,
-                             l->v_pad, stream)))
+              ob_ce_bwd_bf16(s.logits, s.labs, s.lse, dout, B, Sq, V,
+                             l->plan.v_pad, stream)))
     return 1;
   // dW_lm on the side stream (overlaps d_lnout + ln backward below):
   // transpose dlogits and lnf so the GEMM runs on the glds path; tile
@@ -1375,22 +1203,21 @@ static int final_backward_bf16(ob_layer* l, int slot, const float* dout,
     void* const side = (void*)g_side.stream;
     // direct TN via hipBLASLt: M = V with lda = v_pad skips the pad
     // rows entirely (no store guard, no 826 MB logits transpose)
-    static const bool no_lt = ob_env_flag("OB_NO_BLASLT", false);
     int r = -1;
-    if (!no_lt)
+    if (!no_blaslt())
       r = OB_PROF(OB_PF_GEMM_DW, side,
                   ob_gemm_lt(dwlm.tA, dwlm.tB, dwlm.M, dwlm.N, dwlm.K, 1.f,
-                             logits, dwlm.lda, lnf, dwlm.ldb, 1.f, g + 2 * H,
-                             dwlm.ldc, dwlm.c_f32, side));
+                             s.logits, dwlm.lda, s.lnf, dwlm.ldb, 1.f,
+                             g + 2 * H, dwlm.ldc, dwlm.c_f32, side));
     if (r > 0) return 1;
     if (r < 0) {
-      __bf16* DLT = (__bf16*)g_ws.s1;
-      __bf16* LNT = (__bf16*)g_ws.s2;
-      if (ob_transpose_bf16(logits, DLT, BS, l->v_pad, side)) return 1;
-      if (ob_transpose_bf16(lnf, LNT, BS, H, side)) return 1;
+      __bf16* DLT = ws<__bf16>(WS_DW_A);
+      __bf16* LNT = ws<__bf16>(WS_DW_B);
+      if (ob_transpose_bf16(s.logits, DLT, BS, l->plan.v_pad, side)) return 1;
+      if (ob_transpose_bf16(s.lnf, LNT, BS, H, side)) return 1;
       ob_bf16_gemm dw;
       dw.A = DLT, dw.lda = BS, dw.B = LNT, dw.ldb = BS;
-      dw.C = g + 2 * H, dw.ldc = H, dw.M = l->v_pad, dw.N = H, dw.K = BS;
+      dw.C = g + 2 * H, dw.ldc = H, dw.M = l->plan.v_pad, dw.N = H, dw.K = BS;
       dw.out_kind = 2, dw.splitk = ob_deterministic() ? 1 : 2, dw.Mr = V;
       dw.stream = side;
       if (OB_PROF(OB_PF_GEMM_DW, side, ob_gemm_bf16_nt_dispatch(dw)))
@@ -1399,16 +1226,16 @@ static int final_backward_bf16(ob_layer* l, int slot, const float* dout,
   }
   // d_lnout: K = v_pad (padded dlogits cols and shadow^T cols are zero)
   if (OB_PROF(OB_PF_GEMM_DX, stream,
-              linear_bf(lg[LG_DLNOUT], logits, l->shadows + l->sh_lm_t,
-                        nullptr, nullptr, DLN, stream)))
+              linear_bf(lg[LG_DLNOUT], s.logits, shadow(l, SH_LM_T),
+                        nullptr, nullptr, w.DLN, stream)))
     return 1;
+  float* const wsm = ob_deterministic() ? ws<float>(WS_DET_MAIN) : nullptr;
   if (OB_PROF(OB_PF_LN, stream,
-              ob_layernorm_bwd_ws(x, p + 0, st + l->o_mean1, st + l->o_rstd1,
-                                  DLN, din, g + 0, g + H, BS, H, 0,
-                                  ob_deterministic() ? g_ws.det_main : nullptr,
-                                  stream)))
+              ob_layernorm_bwd_ws(s.x, p + 0, s.mean, s.rstd, w.DLN, din,
+                                  g + 0, g + H, BS, H, 0, wsm, stream)))
     return 1;
-  // join: the next backward reuses s1/s2 and reads g on the main stream
+  // join: the next backward reuses the dW buffers and reads g on the main
+  // stream
   OB_SIDE_FENCE(g_side.stream, S(stream));  // join
   return 0;
 }
@@ -1429,7 +1256,7 @@ extern "C" int ob_layer_forward(ob_layer_t l, int32_t slot, const void* in,
     case OB_KIND_EMBED: {
       const int64_t Sq = l->d.seq_len, H = l->d.n_embd, V = l->d.vocab_size;
       const int64_t BS = (int64_t)l->B * Sq;
-      int64_t* ids = l->ids + (int64_t)slot * (int64_t)l->d.max_batch * Sq;
+      int64_t* ids = slot_ids(l, slot);
       OB_HIP(hipMemcpyAsync(ids, in, BS * sizeof(int64_t),
                             hipMemcpyDeviceToDevice, S(stream)));
       if (drop)
@@ -1471,26 +1298,11 @@ static int block_backward(ob_layer* l, int slot, const float* dout, float* din,
   const int64_t B = l->B, BS = B * Sq;
   const int64_t hd = H / nh;
   const float scale = 1.f / sqrtf((float)hd);
-  float* st = l->stash + (int64_t)slot * l->slot_stride;
   const float* p = l->params;
+  const BlockStash<float> s(l, slot);
+  const BwdWs<float> w(l);
   float* g = l->grads;
   const BlockParams bp = block_params(H);
-
-  float* x = st + l->o_x;
-  float* ln1 = st + l->o_ln1;
-  float* qkv = st + l->o_qkv;
-  float* P = st + l->o_p;
-  float* am = st + l->o_attnm;
-  float* hmid = st + l->o_hmid;
-  float* ln2 = st + l->o_ln2;
-  float* u = st + l->o_u;
-  float* gact = st + l->o_g;
-
-  float* DY4 = g_ws.b4h;    // [BS,4H]
-  float* DLN = g_ws.bsh1;   // [BS,H]
-  float* DATT = g_ws.bsh2;  // [BS,H]
-  float* DQKV = g_ws.dqkv;  // [BS,3H]
-  float* DP = g_ws.dp;      // [B*nh,S,S]
   // the masks this slot's forward drew, regenerated from its tick
   const bool dA = l->slot_drop[slot] && l->p_attn > 0.f;
   const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;
@@ -1504,131 +1316,120 @@ static int block_backward(ob_layer* l, int slot, const float* dout, float* din,
   const float* dmlp = dout;
   if (dR) {
     if (ob_drop_scale_colsum(drop_key(l, slot, OB_DROP_RESID_MLP, l->p_resid),
-                             0, dout, g_ws.dm2, g + bp.b_mlpproj, BS, H,
-                             stream))
+                             0, dout, w.dm2, g + bp.b_mlpproj, BS, H, stream))
       return 1;
-    dmlp = g_ws.dm2;
+    dmlp = w.dm2;
   }
   // dg = dout @ w_mlpproj^T
   if (gemm(0, 1, BS, 4 * H, H, 1.f, dmlp, H, 0, 0, p + bp.w_mlpproj, H, 0, 0,
-           0.f, DY4, 4 * H, 0, 0, 1, 1, nullptr, nullptr, 0, 1, stream))
+           0.f, w.DY4, 4 * H, 0, 0, 1, 1, nullptr, nullptr, 0, 1, stream))
     return 1;
   // dW_mlpproj += g^T @ dout ; db += colsum(dout)
-  if (gemm(1, 0, 4 * H, H, BS, 1.f, gact, 4 * H, 0, 0, dmlp, H, 0, 0, 1.f,
+  if (gemm(1, 0, 4 * H, H, BS, 1.f, s.gact, 4 * H, 0, 0, dmlp, H, 0, 0, 1.f,
            g + bp.w_mlpproj, H, 0, 0, 1, 1, nullptr, nullptr, 1,
            pick_splitk(4 * H, H, BS), stream))
     return 1;
   if (!dR && ob_colsum_f32(dout, g + bp.b_mlpproj, BS, H, stream)) return 1;
   // du = dg * gelu'(u)   (in place on DY4)
-  if (ob_gelu_bwd_f32(u, DY4, DY4, BS * 4 * H, stream)) return 1;
+  if (ob_gelu_bwd_f32(s.u, w.DY4, w.DY4, BS * 4 * H, stream)) return 1;
   // dW_fc += ln2^T @ du ; db_fc += colsum(du)
-  if (gemm(1, 0, H, 4 * H, BS, 1.f, ln2, H, 0, 0, DY4, 4 * H, 0, 0, 1.f,
+  if (gemm(1, 0, H, 4 * H, BS, 1.f, s.ln2, H, 0, 0, w.DY4, 4 * H, 0, 0, 1.f,
            g + bp.w_fc, 4 * H, 0, 0, 1, 1, nullptr, nullptr, 1,
            pick_splitk(H, 4 * H, BS), stream))
     return 1;
-  if (ob_colsum_f32(DY4, g + bp.b_fc, BS, 4 * H, stream)) return 1;
+  if (ob_colsum_f32(w.DY4, g + bp.b_fc, BS, 4 * H, stream)) return 1;
   // d_ln2out = du @ w_fc^T  (narrow-N: auto split-K)
-  if (gemm_dx_splitk(1, BS, H, 4 * H, 1.f, DY4, 4 * H, p + bp.w_fc, 4 * H,
-                     DLN, H, stream))
+  if (gemm_dx_splitk(1, BS, H, 4 * H, 1.f, w.DY4, 4 * H, p + bp.w_fc, 4 * H,
+                     w.DLN, H, stream))
     return 1;
   // ln2 backward: din += dx ; dw/db accumulate
-  if (ob_layernorm_bwd_f32(hmid, p + bp.ln2_w, st + l->o_mean2,
-                           st + l->o_rstd2, DLN, din, g + bp.ln2_w,
-                           g + bp.ln2_b, BS, H, 1, stream))
+  if (ob_layernorm_bwd_f32(s.hmid, p + bp.ln2_w, s.mean2, s.rstd2, w.DLN, din,
+                           g + bp.ln2_w, g + bp.ln2_b, BS, H, 1, stream))
     return 1;
   // ---- attention projection backward (din now = d_hmid) ----
   const float* dap = din;
   if (dR) {
     if (ob_drop_scale_colsum(drop_key(l, slot, OB_DROP_RESID_ATTN, l->p_resid),
-                             0, din, g_ws.dm1, g + bp.b_attnproj, BS, H,
-                             stream))
+                             0, din, w.dm1, g + bp.b_attnproj, BS, H, stream))
       return 1;
-    dap = g_ws.dm1;
+    dap = w.dm1;
   }
-  if (gemm_dx_splitk(1, BS, H, H, 1.f, dap, H, p + bp.w_attnproj, H, DATT,
+  if (gemm_dx_splitk(1, BS, H, H, 1.f, dap, H, p + bp.w_attnproj, H, w.DATT,
                      H, stream))
     return 1;
-  if (gemm(1, 0, H, H, BS, 1.f, am, H, 0, 0, dap, H, 0, 0, 1.f,
+  if (gemm(1, 0, H, H, BS, 1.f, s.am, H, 0, 0, dap, H, 0, 0, 1.f,
            g + bp.w_attnproj, H, 0, 0, 1, 1, nullptr, nullptr, 1,
            pick_splitk(H, H, BS), stream))
     return 1;
   if (!dR && ob_colsum_f32(din, g + bp.b_attnproj, BS, H, stream)) return 1;
   // ---- attention core backward ----
   // dP = dO @ V^T
-  if (gemm(0, 1, Sq, Sq, hd, 1.f, DATT, H, Sq * H, hd, qkv + 2 * H, 3 * H,
-           Sq * 3 * H, hd, 0.f, DP, Sq, nh * Sq * Sq, Sq * Sq, B, nh, nullptr,
+  if (gemm(0, 1, Sq, Sq, hd, 1.f, w.DATT, H, Sq * H, hd, s.qkv + 2 * H, 3 * H,
+           Sq * 3 * H, hd, 0.f, w.DP, Sq, nh * Sq * Sq, Sq * Sq, B, nh, nullptr,
            nullptr, 0, 1, stream))
     return 1;
   // attention dropout: DP holds dPd.  Regenerate Pd for dV, mask dPd into
   // dP in place; the softmax backward then runs on the stored P.
-  const float* Pv = P;
+  const float* Pv = s.P;
   if (dA) {
     const ob_drop_key ka = drop_key(l, slot, OB_DROP_ATTN, l->p_attn);
-    if (ob_drop_scale(ka, 0, P, g_ws.pd_b, B * nh * Sq * Sq, stream)) return 1;
-    if (ob_drop_scale(ka, 0, DP, DP, B * nh * Sq * Sq, stream)) return 1;
-    Pv = g_ws.pd_b;
+    if (ob_drop_scale(ka, 0, s.P, w.pd, B * nh * Sq * Sq, stream)) return 1;
+    if (ob_drop_scale(ka, 0, w.DP, w.DP, B * nh * Sq * Sq, stream)) return 1;
+    Pv = w.pd;
   }
   // dS = softmax_bwd(P, dP)  in place on DP
-  if (ob_softmax_causal_bwd_f32(P, DP, B * nh, Sq, stream)) return 1;
+  if (ob_softmax_causal_bwd_f32(s.P, w.DP, B * nh, Sq, stream)) return 1;
   // dQ = scale * dS @ K
-  if (gemm(0, 0, Sq, hd, Sq, scale, DP, Sq, nh * Sq * Sq, Sq * Sq, qkv + H,
-           3 * H, Sq * 3 * H, hd, 0.f, DQKV, 3 * H, Sq * 3 * H, hd, B, nh,
+  if (gemm(0, 0, Sq, hd, Sq, scale, w.DP, Sq, nh * Sq * Sq, Sq * Sq, s.qkv + H,
+           3 * H, Sq * 3 * H, hd, 0.f, w.DQKV, 3 * H, Sq * 3 * H, hd, B, nh,
            nullptr, nullptr, 0, 1, stream))
     return 1;
   // dK = scale * dS^T @ Q
-  if (gemm(1, 0, Sq, hd, Sq, scale, DP, Sq, nh * Sq * Sq, Sq * Sq, qkv, 3 * H,
-           Sq * 3 * H, hd, 0.f, DQKV + H, 3 * H, Sq * 3 * H, hd, B, nh,
+  if (gemm(1, 0, Sq, hd, Sq, scale, w.DP, Sq, nh * Sq * Sq, Sq * Sq, s.qkv,
+           3 * H, Sq * 3 * H, hd, 0.f, w.DQKV + H, 3 * H, Sq * 3 * H, hd, B, nh,
            nullptr, nullptr, 0, 1, stream))
     return 1;
   // dV = Pd^T @ dO
-  if (gemm(1, 0, Sq, hd, Sq, 1.f, Pv, Sq, nh * Sq * Sq, Sq * Sq, DATT, H,
-           Sq * H, hd, 0.f, DQKV + 2 * H, 3 * H, Sq * 3 * H, hd, B, nh,
+  if (gemm(1, 0, Sq, hd, Sq, 1.f, Pv, Sq, nh * Sq * Sq, Sq * Sq, w.DATT, H,
+           Sq * H, hd, 0.f, w.DQKV + 2 * H, 3 * H, Sq * 3 * H, hd, B, nh,
            nullptr, nullptr, 0, 1, stream))
     return 1;
   // ---- QKV projection backward ----
-  if (ob_colsum_f32(DQKV, g + bp.b_qkv, BS, 3 * H, stream)) return 1;
-  if (gemm(1, 0, H, 3 * H, BS, 1.f, ln1, H, 0, 0, DQKV, 3 * H, 0, 0, 1.f,
+  if (ob_colsum_f32(w.DQKV, g + bp.b_qkv, BS, 3 * H, stream)) return 1;
+  if (gemm(1, 0, H, 3 * H, BS, 1.f, s.ln1, H, 0, 0, w.DQKV, 3 * H, 0, 0, 1.f,
            g + bp.w_qkv, 3 * H, 0, 0, 1, 1, nullptr, nullptr, 1,
            pick_splitk(H, 3 * H, BS), stream))
     return 1;
-  if (gemm_dx_splitk(1, BS, H, 3 * H, 1.f, DQKV, 3 * H, p + bp.w_qkv, 3 * H,
-                     DLN, H, stream))
+  if (gemm_dx_splitk(1, BS, H, 3 * H, 1.f, w.DQKV, 3 * H, p + bp.w_qkv, 3 * H,
+                     w.DLN, H, stream))
     return 1;
   // ln1 backward: din += dx
-  if (ob_layernorm_bwd_f32(x, p + bp.ln1_w, st + l->o_mean1, st + l->o_rstd1,
-                           DLN, din, g + bp.ln1_w, g + bp.ln1_b, BS, H, 1,
-                           stream))
-    return 1;
-  return 0;
+  return ob_layernorm_bwd_f32(s.x, p + bp.ln1_w, s.mean1, s.rstd1, w.DLN, din,
+                              g + bp.ln1_w, g + bp.ln1_b, BS, H, 1, stream);
 }
 
 static int final_backward(ob_layer* l, int slot, const float* dout, float* din,
                           void* stream) {
   const int64_t Sq = l->d.seq_len, H = l->d.n_embd, V = l->d.vocab_size;
   const int64_t B = l->B, BS = B * Sq;
-  float* st = l->stash + (int64_t)slot * l->slot_stride;
   const float* p = l->params;
+  const FinalStash<float> s(l, slot);
+  const BwdWs<float> w(l);
   float* g = l->grads;
-  float* x = st + l->o_x;
-  float* lnf = st + l->o_ln1;
-  float* logits = st + l->o_logits;  // becomes dlogits in place
-  int64_t* labs = l->ids + (int64_t)slot * (int64_t)l->d.max_batch * Sq;
 
-  if (ob_ce_bwd_f32(logits, labs, st + l->o_lse, (const float*)dout, B, Sq, V,
+  if (ob_ce_bwd_f32(s.logits, s.labs, s.lse, (const float*)dout, B, Sq, V,
                     stream))
     return 1;
   // dW_lm += dlogits^T @ ln_out
-  if (gemm(1, 0, V, H, BS, 1.f, logits, V, 0, 0, lnf, H, 0, 0, 1.f, g + 2 * H,
-           H, 0, 0, 1, 1, nullptr, nullptr, 1, 1, stream))
+  if (gemm(1, 0, V, H, BS, 1.f, s.logits, V, 0, 0, s.lnf, H, 0, 0, 1.f,
+           g + 2 * H, H, 0, 0, 1, 1, nullptr, nullptr, 1, 1, stream))
     return 1;
   // d_lnout = dlogits @ w_lm  (N=H, K=V: auto split-K)
-  if (gemm_dx_splitk(0, BS, H, V, 1.f, logits, V, p + 2 * H, H, g_ws.bsh1, H,
+  if (gemm_dx_splitk(0, BS, H, V, 1.f, s.logits, V, p + 2 * H, H, w.DLN, H,
                      stream))
     return 1;
-  if (ob_layernorm_bwd_f32(x, p + 0, st + l->o_mean1, st + l->o_rstd1,
-                           g_ws.bsh1, din, g + 0, g + H, BS, H, 0, stream))
-    return 1;
-  return 0;
+  return ob_layernorm_bwd_f32(s.x, p + 0, s.mean, s.rstd, w.DLN, din, g + 0,
+                              g + H, BS, H, 0, stream);
 }
 
 extern "C" int ob_layer_backward(ob_layer_t l, int32_t slot, const void* dout,
@@ -1639,7 +1440,7 @@ extern "C" int ob_layer_backward(ob_layer_t l, int32_t slot, const void* dout,
   switch (l->d.kind) {
     case OB_KIND_EMBED: {
       const int64_t Sq = l->d.seq_len, H = l->d.n_embd, V = l->d.vocab_size;
-      int64_t* ids = l->ids + (int64_t)slot * (int64_t)l->d.max_batch * Sq;
+      int64_t* ids = slot_ids(l, slot);
       if (ob_deterministic()) {  // bf16 only: create refuses fp32
         const ob_drop_key ke = drop_key(l, slot, OB_DROP_EMBD, l->p_embd);
         return OB_PROF(OB_PF_ELEM, stream,
