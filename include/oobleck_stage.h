@@ -384,6 +384,47 @@ int64_t ob_gemm_lt_table_size(void);
 int64_t ob_gemm_lt_untuned_uses(void);
 int ob_gemm_lt_plan_index(const int64_t* shape, void* stream);
 
+/* ---- sliced weight grads ------------------------------
+ * A TN weight grad C[M,N] += A[K,M]^T B[K,N] (bf16 operands, fp32 C, ldc ==
+ * N) whose 128 x 128 output tiles are fewer than the device's CUs may run as
+ * s K-slices: one strided-batched library matmul, slice i into slab i of a
+ * [s, M, N] fp32 slab with beta = 0, then k_dw_fold adds the slabs to C in
+ * ascending order.  ob_layer_create measures the sliced forms of a BLOCK's
+ * weight grads beside the unsliced candidates (by itself at most 2 slices)
+ * and the step runs the winner;
+ * OB_DW_SLICES=1 never slices, OB_DW_SLICES=n forces n where the rule admits
+ * it; deterministic mode, OB_LT_TUNE=0 and OB_NO_BLASLT=1 never slice.
+ *
+ * ob_dw_slices_admit (host-only, no GPU call): 1 if the rule admits s slices
+ * of the shape on a device of cus CUs with a slab of slab_floats floats: TN,
+ * fp32 out, beta = 1, no bias, no C-input, bf16 operands, ldc == N, fewer
+ * tiles than CUs, s in {2, 4, 8, 16}, K % s == 0, K / s a multiple of 256 and
+ * at least 1024, s * M * N <= slab_floats.
+ * ob_gemm_lt_dw_sliced: the call with an explicit s, on the caller's stream;
+ * runs s slices if the rule admits them on this device, else the unsliced
+ * library call, and writes the count that ran to *used (may be null).
+ * ob_gemm_lt_tune_slab: ob_gemm_lt_tune for a caller that can run the shape
+ * sliced with a slab of slab_floats floats: the sliced pairs (the first
+ * OB_LT_TUNE_SLICE_N, default 2, candidates of the batched problem per
+ * admitted slice count, each with the fold) are timed in the same rounds.
+ * ob_gemm_lt_tune itself tunes unsliced.
+ * ob_gemm_lt_slices: the sliced side of a shape's table entry.  out[6] =
+ * {has an entry, the slice count the step runs (1 unsliced), the batched
+ * problem's solution index (-1 unsliced), the fastest sliced pair's median
+ * microseconds (matmul + fold, 0 if none was timed), the milliseconds the
+ * sliced candidates added to the shape's tuning time, that fastest pair's
+ * slice count}; every sliced pair timed goes to slices / index / us, fastest
+ * first, up to cap; returns their number (-1 on a null argument). */
+int ob_dw_slices_admit(const int64_t* shape, int s, int cus,
+                       int64_t slab_floats);
+int ob_gemm_lt_dw_sliced(int64_t M, int64_t N, int64_t K, const void* A,
+                         int64_t lda, const void* B, int64_t ldb, void* C,
+                         int64_t ldc, int s, void* slab, int64_t slab_floats,
+                         void* stream, int32_t* used);
+int ob_gemm_lt_tune_slab(const int64_t* shape, int64_t slab_floats);
+int ob_gemm_lt_slices(const int64_t* shape, double* out, int32_t* slices,
+                      int32_t* index, double* us, int cap);
+
 /* Fused causal flash attention on packed bf16 qkv [B, Sq, 3H] (H % nh == 0,
  * head_dim 64 or 128 — the entries dispatch on H / nh —, Sq % 128 == 0)
  * without transposed operand copies: the kernels read the

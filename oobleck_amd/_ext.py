@@ -160,6 +160,15 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.ob_gemm_lt_untuned_uses.argtypes = []
     lib.ob_gemm_lt_untuned_uses.restype = i64
     lib.ob_gemm_lt_plan_index.argtypes = [shape, vp]
+    # sliced weight grads
+    lib.ob_dw_slices_admit.argtypes = [shape, i32, i32, i64]
+    lib.ob_gemm_lt_dw_sliced.argtypes = [i64, i64, i64, vp, i64, vp, i64, vp,
+                                         i64, i32, vp, i64, vp,
+                                         ctypes.POINTER(i32)]
+    lib.ob_gemm_lt_tune_slab.argtypes = [shape, i64]
+    lib.ob_gemm_lt_slices.argtypes = [shape, ctypes.POINTER(ctypes.c_double),
+                                      ctypes.POINTER(i32), ctypes.POINTER(i32),
+                                      ctypes.POINTER(ctypes.c_double), i32]
     lib.ob_profile_enable.argtypes = [i32]
     lib.ob_profile_enable.restype = None
     lib.ob_profile_reset.argtypes = []
@@ -280,6 +289,29 @@ def lt_candidates(shape, cap: int = 128) -> list[dict]:
     n = get_ext().ob_gemm_lt_candidates(lt_shape(*shape), idx, pos, us, cap)
     return [{"index": idx[i], "pos": pos[i], "us": us[i]}
             for i in range(max(0, min(n, cap)))]
+
+
+def dw_slices_admit(shape, s: int, cus: int, slab_floats: int) -> bool:
+    """The rule of ob_dw_slices.h: may this shape run as s K-slices on a
+    device of cus CUs with a slab of slab_floats floats?  No GPU call."""
+    return bool(get_ext().ob_dw_slices_admit(lt_shape(*shape), s, cus,
+                                             slab_floats))
+
+
+def lt_slices(shape, cap: int = 32) -> dict | None:
+    """The sliced side of a shape's table entry (ob_gemm_lt_slices), or
+    None."""
+    out = (ctypes.c_double * 6)()
+    sl, idx = (ctypes.c_int32 * cap)(), (ctypes.c_int32 * cap)()
+    us = (ctypes.c_double * cap)()
+    n = get_ext().ob_gemm_lt_slices(lt_shape(*shape), out, sl, idx, us, cap)
+    if n < 0 or not out[0]:
+        return None
+    return {"slices": int(out[1]), "slice_index": int(out[2]),
+            "us_sliced": out[3], "added_ms": out[4],
+            "fastest_slices": int(out[5]),
+            "pairs": [{"slices": sl[i], "index": idx[i], "us": us[i]}
+                      for i in range(min(n, cap))]}
 
 
 # ob_layer_plan_query's fields, in order (include/oobleck_stage.h)

@@ -23,6 +23,7 @@ HEADERS = [PKG_DIR.parent / "include" / "oobleck_stage.h",
            PKG_DIR / "csrc" / "ob_flash_common.h",
            PKG_DIR / "csrc" / "ob_bf16.h",
            PKG_DIR / "csrc" / "ob_gemm_route.h",
+           PKG_DIR / "csrc" / "ob_dw_slices.h",
            PKG_DIR / "csrc" / "ob_philox.h"]
 
 

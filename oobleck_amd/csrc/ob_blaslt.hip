@@ -22,6 +22,7 @@
 // The tuner is host code called from layer_create and the ob_gemm_lt_tune
 // export, never from a step.  OB_LT_TUNE=0 disables it.
 #include "ob_internal.h"
+#include "ob_dw_slices.h"
 
 #include <hipblaslt/hipblaslt-ext.hpp>
 #include <hipblaslt/hipblaslt.h>
@@ -36,6 +37,8 @@
 #include <set>
 #include <string>
 #include <tuple>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace {
@@ -44,9 +47,12 @@ constexpr size_t kLtWs = 64u << 20;
 
 struct Key {
   ob_lt_shape s;
+  // > 1 (plan caches only): the K-slices of s as one strided-batched problem
+  // of that many entries, beta = 0, each into its own [M, N] slab
+  int batch = 1;
   auto tie() const {
     return std::tie(s.tA, s.tB, s.M, s.N, s.K, s.lda, s.ldb, s.ldc, s.c_f32,
-                    s.beta1, s.bias, s.cin, s.ab_f32);
+                    s.beta1, s.bias, s.cin, s.ab_f32, batch);
   }
   bool operator<(const Key& o) const { return tie() < o.tie(); }
 };
@@ -63,6 +69,8 @@ struct LtPlan {
   int index = -1;
   bool ok = false;
   bool untuned = false;  // built while the choice table had no entry
+  // unsliced plans: the table's slice count for this shape (1: run unsliced)
+  int slices = 1;
 };
 
 // ONE FULL CONTEXT PER STREAM — handle + workspace + plan cache.
@@ -96,6 +104,16 @@ struct LtChoice {
     double us;
   };
   std::vector<Timed> timed;
+  // the sliced call (ob_dw_slices.h): slices > 1 runs the shape as that many
+  // K-slices with solution slice_index of the batched problem, then the fold
+  int slices = 1, slice_index = -1;
+  double us_sliced = 0;  // the fastest sliced pair's median, chosen or not
+  double slice_ms = 0;   // host time the sliced candidates added to wall_ms
+  struct Sliced {
+    int slices, index, pos;
+    double us;  // median of matmul + fold
+  };
+  std::vector<Sliced> sliced;
 };
 std::mutex g_tab_mu;
 std::map<Key, LtChoice> g_tab;
@@ -117,7 +135,12 @@ LtCtx* lt_ctx(void* stream) {
   return &g_lt_by_stream.emplace(stream, ctx).first->second;
 }
 
-void lt_problem_create(const ob_lt_shape& k, const void* bias, LtProblem* p) {
+void lt_problem_create(const ob_lt_shape& k0, const void* bias, LtProblem* p,
+                       int batch = 1) {
+  // batch > 1: entry i is K-slice i of k0, rows i*K/batch on of A and B, and
+  // writes slab i of a dense [batch, M, N] output
+  ob_lt_shape k = k0;
+  if (batch > 1) k.K = k0.K / batch, k.ldc = k0.N;
   // column-major swap: A-slot <- B bytes, B-slot <- A bytes
   const hipblasOperation_t opA = k.tB ? HIPBLAS_OP_T : HIPBLAS_OP_N;
   const hipblasOperation_t opB = k.tA ? HIPBLAS_OP_T : HIPBLAS_OP_N;
@@ -149,6 +172,19 @@ void lt_problem_create(const ob_lt_shape& k, const void* bias, LtProblem* p) {
   hipblasLtMatrixLayoutCreate(&p->lb, abt, b_rows, b_cols, k.lda);
   hipblasLtMatrixLayoutCreate(&p->lc, k.c_f32 ? HIP_R_32F : HIP_R_16BF, k.N,
                               k.M, k.ldc);
+  if (batch > 1) {
+    const int32_t n = batch;
+    const int64_t sa = k.K * k.ldb, sb = k.K * k.lda, sc = k.M * k.N;
+    const std::pair<hipblasLtMatrixLayout_t, int64_t> ls[] = {
+        {p->la, sa}, {p->lb, sb}, {p->lc, sc}};
+    for (const auto& l : ls) {
+      hipblasLtMatrixLayoutSetAttribute(
+          l.first, HIPBLASLT_MATRIX_LAYOUT_BATCH_COUNT, &n, sizeof(n));
+      hipblasLtMatrixLayoutSetAttribute(
+          l.first, HIPBLASLT_MATRIX_LAYOUT_STRIDED_BATCH_OFFSET, &l.second,
+          sizeof(l.second));
+    }
+  }
 }
 
 void lt_problem_destroy(LtProblem* p) {
@@ -176,14 +212,13 @@ int lt_heuristic(hipblasLtHandle_t h, const LtProblem& p, int n,
 
 // the table's solution for this handle and problem, if it still fits
 bool lt_algo_from_index(hipblasLtHandle_t h, const LtProblem& p,
-                        const ob_lt_shape& k, int index,
-                        hipblasLtMatmulAlgo_t* algo) {
+                        float beta, int index, hipblasLtMatmulAlgo_t* algo) {
   std::vector<int> idx{index};
   std::vector<hipblasLtMatmulHeuristicResult_t> r;
   if (hipblaslt_ext::getAlgosFromIndex(h, idx, r) != HIPBLAS_STATUS_SUCCESS ||
       r.empty())
     return false;
-  const float alpha = 1.f, beta = k.beta1 ? 1.f : 0.f;
+  const float alpha = 1.f;
   size_t need = 0;
   if (hipblaslt_ext::matmulIsAlgoSupported(h, p.desc, &alpha, p.la, p.lb,
                                            &beta, p.lc, p.lc, r[0].algo,
@@ -196,17 +231,24 @@ bool lt_algo_from_index(hipblasLtHandle_t h, const LtProblem& p,
 
 LtPlan lt_plan_build(LtCtx* ctx, const Key& key, const void* bias) {
   LtPlan p;
-  lt_problem_create(key.s, bias, &p.p);
+  lt_problem_create(key.s, bias, &p.p, key.batch);
   int index = -1;
   {
+    // the table is keyed by the unsliced shape; a sliced plan takes the
+    // table's batched solution when it was measured for this slice count
     std::lock_guard<std::mutex> lk(g_tab_mu);
-    auto it = g_tab.find(key);
-    if (it == g_tab.end())
-      p.untuned = lt_tune_on();
-    else if (it->second.tuned && lt_tune_on())
-      index = it->second.index;
+    auto it = g_tab.find(Key{key.s});
+    if (it == g_tab.end()) {
+      p.untuned = lt_tune_on() && key.batch == 1;
+    } else if (it->second.tuned && lt_tune_on()) {
+      if (key.batch == 1)
+        index = it->second.index, p.slices = it->second.slices;
+      else if (it->second.slices == key.batch)
+        index = it->second.slice_index;
+    }
   }
-  if (index >= 0 && lt_algo_from_index(ctx->h, p.p, key.s, index, &p.algo)) {
+  const float beta = key.batch == 1 && key.s.beta1 ? 1.f : 0.f;
+  if (index >= 0 && lt_algo_from_index(ctx->h, p.p, beta, index, &p.algo)) {
     p.index = index;
     p.ok = true;
     return p;
@@ -219,6 +261,86 @@ LtPlan lt_plan_build(LtCtx* ctx, const Key& key, const void* bias) {
     p.ok = true;
   }
   return p;
+}
+
+// ---- sliced weight grads (ob_dw_slices.h) ----------------
+
+// OB_DW_SLICES (read once): 0 / unset the tuner decides, 1 never slice, n
+// force n slices wherever the rule admits them (probing)
+int dw_slices_env() {
+  static const int n = ob_env_int("OB_DW_SLICES", 0);
+  return n < 0 ? 0 : n;
+}
+
+// CUs of the current device; 0 (nothing is sliced) if it cannot be asked
+int lt_cus() {
+  static const int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount,
+                              dev) != hipSuccess)
+      return 0;
+    return v;
+  }();
+  return n;
+}
+
+ob_dw_slice_shape dw_slice_shape(const ob_lt_shape& k) {
+  return {k.tA, k.tB, k.c_f32, k.beta1, !k.bias && !k.cin && !k.ab_f32,
+          k.M,  k.N,  k.K,     k.ldc};
+}
+
+// The fold of a sliced weight grad: g[j] += slab[0][j] + ... + slab[S-1][j]
+// for j < n, the slabs n floats apart.  The slabs are summed in ascending
+// order in fp32 and the total is added to g once; one thread owns its W
+// elements, so there are no atomics and the result depends on S alone.  All
+// S + 1 loads are issued before the first add.  W = 4 needs g and slab
+// 16-byte aligned and n % 4 == 0.  Bound by memory: (S + 2) * 4n bytes.
+// (Outside the unnamed namespace so that profiles show it by name.)
+}  // namespace
+
+template <int S, int W>
+__global__ __launch_bounds__(256) void k_dw_fold(float* __restrict__ g,
+                                                 const float* __restrict__ slab,
+                                                 int64_t n) {
+  using V = typename std::conditional<W == 4, float4, float>::type;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n / W) return;
+  V v[S];
+#pragma unroll
+  for (int k = 0; k < S; k++)
+    v[k] = reinterpret_cast<const V*>(slab + (int64_t)k * n)[i];
+  V acc = reinterpret_cast<const V*>(g)[i];
+  V t = v[0];
+#pragma unroll
+  for (int k = 1; k < S; k++) t += v[k];
+  acc += t;
+  reinterpret_cast<V*>(g)[i] = acc;
+}
+
+namespace {
+
+template <int W>
+int dw_fold_w(float* g, const float* slab, int s, int64_t n, hipStream_t st) {
+  const int64_t blocks = (n / W + 255) / 256;
+  if (blocks > INT32_MAX) return ob_fail("dw_fold: output too large");
+  const dim3 grid((unsigned)blocks);
+  switch (s) {
+    case 2: k_dw_fold<2, W><<<grid, 256, 0, st>>>(g, slab, n); break;
+    case 4: k_dw_fold<4, W><<<grid, 256, 0, st>>>(g, slab, n); break;
+    case 8: k_dw_fold<8, W><<<grid, 256, 0, st>>>(g, slab, n); break;
+    case 16: k_dw_fold<16, W><<<grid, 256, 0, st>>>(g, slab, n); break;
+    default: return ob_fail("dw_fold: %d slices", s);
+  }
+  OB_LAUNCH_CHECK();
+  return 0;
+}
+
+int dw_fold(float* g, const float* slab, int s, int64_t n, hipStream_t st) {
+  if (n <= 0) return 0;
+  const bool vec = n % 4 == 0 && (uintptr_t)g % 16 == 0 &&
+                   (uintptr_t)slab % 16 == 0;
+  return vec ? dw_fold_w<4>(g, slab, s, n, st) : dw_fold_w<1>(g, slab, s, n, st);
 }
 
 // ---- tuner ----------------------------------------------------------------
@@ -274,13 +396,15 @@ struct TuneScratch {
   hipStream_t stream = nullptr;
   hipblasLtHandle_t h = nullptr;
   void *ws = nullptr, *A = nullptr, *B = nullptr, *C = nullptr, *Cref = nullptr,
-       *Cin = nullptr, *bias = nullptr;
+       *Cin = nullptr, *bias = nullptr, *slab = nullptr;
   double* acc = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   LtProblem p;
+  std::vector<LtProblem> sp;  // the batched problems, one per slice count
   ~TuneScratch() {
     lt_problem_destroy(&p);
-    for (void* q : {ws, A, B, C, Cref, Cin, bias, (void*)acc})
+    for (LtProblem& q : sp) lt_problem_destroy(&q);
+    for (void* q : {ws, A, B, C, Cref, Cin, bias, slab, (void*)acc})
       if (q) (void)hipFree(q);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
@@ -292,6 +416,7 @@ struct TuneScratch {
 struct Cand {
   hipblasLtMatmulAlgo_t algo;
   int pos = 0;  // position in the candidate list
+  int slices = 1, prob = -1;  // > 1: a sliced pair on batched problem sp[prob]
   int reps = 1;
   float warm_us = 0.f;
   std::vector<float> us;  // per round, per call
@@ -299,8 +424,11 @@ struct Cand {
 
 // Measures the heuristic's candidates for one shape and fills *out.  Returns
 // false when tuning was abandoned (allocation failure or any HIP error):
-// the caller keeps top-1.
-bool lt_tune_run(const ob_lt_shape& k, LtChoice* out) {
+// the caller keeps top-1.  slab_floats > 0: the caller can run the shape
+// sliced with a slab that large, so for every slice count the rule admits
+// the first candidates of the batched problem, each followed by the fold,
+// are measured in the same rounds.
+bool lt_tune_run(const ob_lt_shape& k, int64_t slab_floats, LtChoice* out) {
   const int n_env = ob_env_int("OB_LT_TUNE_N", 8);
   const int n_max = n_env < 1 ? 1 : n_env > 128 ? 128 : n_env;
   constexpr int kRounds = 5;
@@ -369,26 +497,89 @@ bool lt_tune_run(const ob_lt_shape& k, LtChoice* out) {
     }
   }
   const int nres = (int)res.size();
+  std::vector<Cand> listed;
+  for (int i = 0; i < nres; i++) {
+    if (res[i].state != HIPBLAS_STATUS_SUCCESS) {
+      out->dropped++;
+      continue;
+    }
+    Cand c;
+    c.algo = res[i].algo;
+    c.pos = i;
+    listed.push_back(c);
+  }
+  // candidate 0, the reference of the gate and of the hysteresis, is the
+  // heuristic's first unsliced answer; without one the shape is abandoned
+  if (listed.empty() || listed[0].pos != 0 || listed[0].slices != 1)
+    return false;
+  // the sliced pairs: per admissible slice count, the first OB_LT_TUNE_SLICE_N
+  // (default 2) candidates of the batched problem.  OB_DW_SLICES=1 lists
+  // none, OB_DW_SLICES=n only those of n slices.
+  const auto ts0 = std::chrono::steady_clock::now();
+  auto since = [](std::chrono::steady_clock::time_point a) {
+    return std::chrono::duration<double, std::milli>(
+               std::chrono::steady_clock::now() - a)
+        .count();
+  };
+  const int forced = dw_slices_env();
+  int slist[4], ns = 0;
+  if (slab_floats > 0 && forced != 1)
+    ns = ob_dw_slices_list(dw_slice_shape(k), lt_cus(), slab_floats, slist);
+  if (ns > 0) {
+    const int per_env = ob_env_int("OB_LT_TUNE_SLICE_N", 2);
+    const int per = per_env < 1 ? 1 : per_env > 8 ? 8 : per_env;
+    int smax = 0;
+    for (int j = 0; j < ns; j++) {
+      const int s = slist[j];
+      if (forced > 1 ? s != forced : s > OB_DW_SLICES_AUTO_MAX) continue;
+      t.sp.emplace_back();
+      lt_problem_create(k, nullptr, &t.sp.back(), s);
+      hipblasLtMatmulHeuristicResult_t sres[8];
+      const int got = lt_heuristic(t.h, t.sp.back(), per, sres);
+      for (int i = 0; i < got; i++) {
+        if (sres[i].state != HIPBLAS_STATUS_SUCCESS) continue;
+        Cand c;
+        c.algo = sres[i].algo;
+        c.pos = i, c.slices = s, c.prob = (int)t.sp.size() - 1;
+        listed.push_back(c);
+        smax = s;
+      }
+    }
+    if (smax) LT_TRY(hipMalloc(&t.slab, (size_t)smax * k.M * k.N * 4));
+  }
+  out->slice_ms += since(ts0);
   // one call; into dst for the gate, into C when timing.  A beta=1 call
-  // without a separate C-input accumulates into its (zeroed) output.
-  auto run = [&](hipblasLtMatmulAlgo_t& algo, void* dst) {
+  // without a separate C-input accumulates into its (zeroed) output.  A
+  // sliced pair is the batched beta=0 matmul into the slab and the fold of
+  // the slab into dst.
+  const float zero = 0.f;
+  auto run = [&](Cand& c, void* dst) {
+    if (c.slices > 1) {
+      const LtProblem& q = t.sp[c.prob];
+      const hipblasStatus_t st = hipblasLtMatmul(
+          t.h, q.desc, &alpha, t.B, q.la, t.A, q.lb, &zero, t.slab, q.lc,
+          t.slab, q.lc, &c.algo, t.ws, kLtWs, t.stream);
+      if (st != HIPBLAS_STATUS_SUCCESS) return st;
+      return dw_fold((float*)dst, (const float*)t.slab, c.slices, k.M * k.N,
+                     t.stream)
+                 ? HIPBLAS_STATUS_INTERNAL_ERROR
+                 : HIPBLAS_STATUS_SUCCESS;
+    }
     return hipblasLtMatmul(t.h, t.p.desc, &alpha, t.B, t.p.la, t.A, t.p.lb,
                            &beta, t.Cin ? t.Cin : dst, t.p.lc, dst, t.p.lc,
-                           &algo, t.ws, kLtWs, t.stream);
+                           &c.algo, t.ws, kLtWs, t.stream);
   };
   // correctness gate: every candidate once, against candidate 0's output on
   // the same inputs.  Both are exact bf16 products summed in fp32 in another
   // order: one output ulp for bf16, the project's rtol for fp32 accumulation.
   const double bound = k.c_f32 ? 1e-3 : 1.0 / 256;
   std::vector<Cand> cands;
-  for (int i = 0; i < nres; i++) {
-    if (res[i].state != HIPBLAS_STATUS_SUCCESS) {
-      out->dropped++;
-      continue;
-    }
+  for (size_t i = 0; i < listed.size(); i++) {
+    const auto tc0 = std::chrono::steady_clock::now();
+    const bool sliced = listed[i].slices > 1;
     void* dst = i == 0 ? t.Cref : t.C;
     LT_TRY(hipMemsetAsync(dst, 0, nC * es_c, t.stream));
-    const hipblasStatus_t st = run(res[i].algo, dst);
+    const hipblasStatus_t st = run(listed[i], dst);
     if (i == 0 && st != HIPBLAS_STATUS_SUCCESS) return false;
     if (st != HIPBLAS_STATUS_SUCCESS) {
       LT_TRY(hipStreamSynchronize(t.stream));
@@ -411,10 +602,8 @@ bool lt_tune_run(const ob_lt_shape& k, LtChoice* out) {
     } else {
       LT_TRY(hipStreamSynchronize(t.stream));
     }
-    Cand c;
-    c.algo = res[i].algo;
-    c.pos = i;
-    cands.push_back(c);
+    cands.push_back(listed[i]);
+    if (sliced) out->slice_ms += since(tc0);
   }
   out->tried = nres;
   // a visit: events around reps back-to-back calls, read only after the
@@ -426,7 +615,7 @@ bool lt_tune_run(const ob_lt_shape& k, LtChoice* out) {
     if (hipEventRecord(t.e0, t.stream) != hipSuccess) return (int)V_HIP;
     bool lib_ok = true;
     for (int r = 0; r < reps && lib_ok; r++)
-      lib_ok = run(c.algo, t.C) == HIPBLAS_STATUS_SUCCESS;
+      lib_ok = run(c, t.C) == HIPBLAS_STATUS_SUCCESS;
     float ms = 0.f;
     if (hipEventRecord(t.e1, t.stream) != hipSuccess ||
         hipEventSynchronize(t.e1) != hipSuccess ||
@@ -453,23 +642,28 @@ bool lt_tune_run(const ob_lt_shape& k, LtChoice* out) {
   // a window of 1.25 ms
   for (size_t i = 0; i < cands.size();) {
     Cand& c = cands[i];
+    const auto tc0 = std::chrono::steady_clock::now();
     float us = 0.f;
     int v = visit(c, 1, &us);
     if (v == V_OK) v = visit(c, 8, &us);
+    if (c.slices > 1) out->slice_ms += since(tc0);
     if (v == V_HIP || (v == V_DROP && !drop(i))) return false;
     if (v == V_DROP) continue;
     c.warm_us = us;
     c.reps = reps_for(us);
     i++;
   }
-  // a list longer than n_max (OB_LT_TUNE_ALL): the rounds go to candidate 0
-  // and the n_max - 1 fastest of the warm visits
-  if ((int)cands.size() > n_max) {
-    std::stable_sort(cands.begin() + 1, cands.end(),
+  // an unsliced list longer than n_max (OB_LT_TUNE_ALL): the rounds go to
+  // candidate 0 and the n_max - 1 fastest of the warm visits (the sliced
+  // pairs stand behind the unsliced candidates and all stay)
+  const int n_unsl = (int)std::count_if(
+      cands.begin(), cands.end(), [](const Cand& c) { return c.slices == 1; });
+  if (n_unsl > n_max) {
+    std::stable_sort(cands.begin() + 1, cands.begin() + n_unsl,
                      [](const Cand& a, const Cand& b) {
                        return a.warm_us < b.warm_us;
                      });
-    cands.resize(n_max);
+    cands.erase(cands.begin() + n_max, cands.begin() + n_unsl);
   }
   // rounds visit all candidates round-robin, so clock drift and neighbours
   // hit them alike.  A window that came out under 1 ms is not scored: reps
@@ -477,6 +671,7 @@ bool lt_tune_run(const ob_lt_shape& k, LtChoice* out) {
   for (int r = 0; r < kRounds; r++)
     for (size_t i = 0; i < cands.size();) {
       Cand& c = cands[i];
+      const auto tc0 = std::chrono::steady_clock::now();
       float us = 0.f;
       int v = V_OK;
       for (int attempt = 0; attempt < 4; attempt++) {
@@ -484,6 +679,7 @@ bool lt_tune_run(const ob_lt_shape& k, LtChoice* out) {
         if (v != V_OK || us * c.reps >= 1000.f || c.reps >= 4096) break;
         c.reps = std::max(c.reps + 1, reps_for(us));
       }
+      if (c.slices > 1) out->slice_ms += since(tc0);
       if (v == V_HIP || (v == V_DROP && !drop(i))) return false;
       if (v == V_DROP) continue;
       c.us.push_back(us);
@@ -503,7 +699,7 @@ bool lt_tune_run(const ob_lt_shape& k, LtChoice* out) {
   double best_med = med0;
   out->timed.push_back(
       {hipblaslt_ext::getIndexFromAlgo(cands[0].algo), 0, med0});
-  for (size_t i = 1; i < cands.size(); i++) {
+  for (size_t i = 1; i < cands.size() && cands[i].slices == 1; i++) {
     const double m = median_of(cands[i].us);
     out->timed.push_back(
         {hipblaslt_ext::getIndexFromAlgo(cands[i].algo), cands[i].pos, m});
@@ -520,6 +716,31 @@ bool lt_tune_run(const ob_lt_shape& k, LtChoice* out) {
   out->us_chosen = best_med;
   out->index = hipblaslt_ext::getIndexFromAlgo(cands[best].algo);
   out->chosen_name = hipblaslt_ext::getKernelNameFromAlgo(t.h, cands[best].algo);
+  // the sliced pairs, by the same hysteresis: the shape stays unsliced unless
+  // the fastest pair's median beats top-1's by more than top-1's spread, won
+  // every round against top-1, and is under the chosen unsliced median too.
+  // OB_DW_SLICES=n takes the fastest pair of n slices as it is.
+  size_t sbest = 0;
+  double sbest_med = 0;
+  for (size_t i = 1; i < cands.size(); i++) {
+    if (cands[i].slices == 1) continue;
+    const double m = median_of(cands[i].us);
+    out->sliced.push_back({cands[i].slices,
+                           hipblaslt_ext::getIndexFromAlgo(cands[i].algo),
+                           cands[i].pos, m});
+    if (!sbest || m < sbest_med) sbest_med = m, sbest = i;
+  }
+  if (sbest) {
+    out->us_sliced = sbest_med;
+    const bool wins =
+        sbest_med < med0 - spread0 && sbest_med < best_med &&
+        *std::max_element(cands[sbest].us.begin(), cands[sbest].us.end()) <
+            min0;
+    if (wins || forced > 1) {
+      out->slices = cands[sbest].slices;
+      out->slice_index = hipblaslt_ext::getIndexFromAlgo(cands[sbest].algo);
+    }
+  }
   out->tuned = true;
   return true;
 }
@@ -536,7 +757,7 @@ Key key_from_i64(const int64_t* v) {
 
 }  // namespace
 
-int ob_lt_tune_shape(const ob_lt_shape& s) {
+int ob_lt_tune_shape(const ob_lt_shape& s, int64_t slab_floats) {
   if (!lt_tune_on()) return 0;
   if (s.M <= 0 || s.N <= 0 || s.K <= 0 || s.ldc < s.N ||
       s.lda < (s.tA ? s.M : s.K) || s.ldb < (s.tB ? s.K : s.N))
@@ -550,7 +771,7 @@ int ob_lt_tune_shape(const ob_lt_shape& s) {
   OB_HIP(hipDeviceSynchronize());
   const auto t0 = std::chrono::steady_clock::now();
   LtChoice c;
-  if (!lt_tune_run(s, &c)) {
+  if (!lt_tune_run(s, slab_floats, &c)) {
     // abandoned: the entry stays untuned (plans use top-1) and is not retried
     c.tuned = false;
     c.index = c.top1_index;
@@ -565,12 +786,13 @@ int ob_lt_tune_shape(const ob_lt_shape& s) {
     g_tab.emplace(key, c);
   }
   // plans built for this shape before it had an entry are rebuilt
-  for (auto& sc : g_lt_by_stream) {
-    auto it = sc.second.plans.find(key);
-    if (it == sc.second.plans.end()) continue;
-    lt_problem_destroy(&it->second.p);
-    sc.second.plans.erase(it);
-  }
+  for (auto& sc : g_lt_by_stream)
+    for (int batch = 1; batch <= OB_DW_SLICES_MAX; batch *= 2) {
+      auto it = sc.second.plans.find(Key{s, batch});
+      if (it == sc.second.plans.end()) continue;
+      lt_problem_destroy(&it->second.p);
+      sc.second.plans.erase(it);
+    }
   return 0;
 }
 
@@ -584,6 +806,14 @@ int ob_lt_tune_shape(const ob_lt_shape& s) {
 // Cin: the C-INPUT operand (D = alpha*op(A)op(B) + beta*Cin, written to
 // C) — hipblasLt supports C != D, which folds a residual WITHOUT the
 // 12.6 MB copy the round-1 path paid per forward projection GEMM.
+static const LtPlan* lt_plan_get(LtCtx* ctx, const Key& key,
+                                 const void* bias) {
+  auto it = ctx->plans.find(key);
+  if (it == ctx->plans.end())
+    it = ctx->plans.emplace(key, lt_plan_build(ctx, key, bias)).first;
+  return &it->second;
+}
+
 static int lt_matmul(int tA, int tB, int64_t M, int64_t N, int64_t K,
                      float alpha, const void* A, int64_t lda, const void* B,
                      int64_t ldb, float beta, void* C, int64_t ldc,
@@ -594,10 +824,7 @@ static int lt_matmul(int tA, int tB, int64_t M, int64_t N, int64_t K,
   if (!ctx) return ob_fail("hipblasLt per-stream context init failed");
   const Key key{ob_lt_shape_of(tA, tB, M, N, K, lda, ldb, ldc, c_f32, beta,
                                bias != nullptr, Cin != C, ab_f32)};
-  auto it = ctx->plans.find(key);
-  if (it == ctx->plans.end())
-    it = ctx->plans.emplace(key, lt_plan_build(ctx, key, bias)).first;
-  const LtPlan& p = it->second;
+  const LtPlan& p = *lt_plan_get(ctx, key, bias);
   if (!p.ok) return -1;
   if (p.untuned) g_untuned_uses.fetch_add(1, std::memory_order_relaxed);
   if (bias)
@@ -609,6 +836,83 @@ static int lt_matmul(int tA, int tB, int64_t M, int64_t N, int64_t K,
   if (st != HIPBLAS_STATUS_SUCCESS)
     return ob_fail("hipblasLtMatmul failed (%d)", (int)st);
   return 0;
+}
+
+// The sliced form of a TN weight grad C[M,N] += A[K,M]^T B[K,N]: one
+// strided-batched matmul whose entry i is K-slice i, beta = 0, into slab i of
+// slab[n, M, N], then k_dw_fold adds the slabs to C.  The caller has asked
+// the rule (ob_dw_slices_ok), so ldc == N and the slab holds n * M * N
+// floats.  -1, with nothing enqueued, if the library has no solution.
+static int lt_dw_sliced(LtCtx* ctx, const ob_lt_shape& s, int n, const void* A,
+                        const void* B, float* C, float* slab, void* stream) {
+  const LtPlan& p = *lt_plan_get(ctx, Key{s, n}, nullptr);
+  if (!p.ok) return -1;
+  const float one = 1.f, zero = 0.f;
+  const hipblasStatus_t st = hipblasLtMatmul(
+      ctx->h, p.p.desc, &one, B, p.p.la, A, p.p.lb, &zero, slab, p.p.lc, slab,
+      p.p.lc, &p.algo, ctx->ws, kLtWs, reinterpret_cast<hipStream_t>(stream));
+  if (st != HIPBLAS_STATUS_SUCCESS)
+    return ob_fail("hipblasLtMatmul (sliced) failed (%d)", (int)st);
+  return dw_fold(C, slab, n, s.M * s.N, reinterpret_cast<hipStream_t>(stream));
+}
+
+// The layer's weight grad (dw_bf16_ws): sliced when the choice table says so
+// for this shape and the slab still fits, else the plain beta = 1 call.  A
+// call either slices or runs unsliced, never both.
+int ob_lt_dw_run(const ob_lt_shape& s, const void* act, const void* dY,
+                 float* gout, float* slab, int64_t slab_floats, void* stream) {
+  LtCtx* ctx = lt_ctx(stream);
+  if (!ctx) return ob_fail("hipblasLt per-stream context init failed");
+  // the unsliced plan is built (and kept) for a sliced shape too: it carries
+  // the table's slice count, and it is what runs if the slab no longer fits
+  const int n = lt_plan_get(ctx, Key{s}, nullptr)->slices;
+  if (n > 1 && slab &&
+      ob_dw_slices_ok(dw_slice_shape(s), n, lt_cus(), slab_floats)) {
+    const int r = lt_dw_sliced(ctx, s, n, act, dY, gout, slab, stream);
+    if (r >= 0) return r;
+  }
+  return lt_matmul(s.tA, s.tB, s.M, s.N, s.K, 1.f, act, s.lda, dY, s.ldb, 1.f,
+                   gout, s.ldc, s.c_f32, nullptr, 0, stream);
+}
+
+// The sliced weight grad with an explicit slice count (tests, probes):
+// C[M,N] += A[K,M]^T B[K,N], bf16 operands, fp32 C.  s slices if the rule
+// admits them on this device with this slab, else unsliced; *used (optional)
+// gets the count that ran.  The choice table and OB_DW_SLICES play no part.
+extern "C" int ob_gemm_lt_dw_sliced(int64_t M, int64_t N, int64_t K,
+                                    const void* A, int64_t lda, const void* B,
+                                    int64_t ldb, void* C, int64_t ldc, int s,
+                                    void* slab, int64_t slab_floats,
+                                    void* stream, int32_t* used) {
+  if (!A || !B || !C) return ob_fail("gemm_lt_dw_sliced: null operand");
+  if (M <= 0 || N <= 0 || K <= 0 || lda < M || ldb < N || ldc < N)
+    return ob_fail("gemm_lt_dw_sliced: bad shape");
+  const ob_lt_shape k = ob_lt_dw(M, N, K, lda);
+  ob_lt_shape kk = k;
+  kk.ldb = ldb, kk.ldc = ldc;
+  if (used) *used = 1;
+  LtCtx* ctx = lt_ctx(stream);
+  if (!ctx) return ob_fail("hipblasLt per-stream context init failed");
+  if (slab && ob_dw_slices_ok(dw_slice_shape(kk), s, lt_cus(), slab_floats)) {
+    const int r =
+        lt_dw_sliced(ctx, kk, s, A, B, (float*)C, (float*)slab, stream);
+    if (r == 0 && used) *used = s;
+    if (r >= 0) return r;
+  }
+  const int r = lt_matmul(1, 0, M, N, K, 1.f, A, lda, B, ldb, 1.f, C, ldc, 1,
+                          nullptr, 0, stream);
+  return r < 0 ? ob_fail("gemm_lt_dw_sliced: the library has no solution") : r;
+}
+
+// host-only: does the rule (ob_dw_slices.h) admit s slices of this shape on a
+// device of cus CUs with a slab of slab_floats floats?
+extern "C" int ob_dw_slices_admit(const int64_t* shape, int s, int cus,
+                                  int64_t slab_floats) {
+  if (!shape) return 0;
+  return ob_dw_slices_ok(dw_slice_shape(key_from_i64(shape).s), s, cus,
+                         slab_floats)
+             ? 1
+             : 0;
 }
 
 extern "C" int ob_gemm_lt(int tA, int tB, int64_t M, int64_t N, int64_t K,
@@ -657,6 +961,15 @@ extern "C" int ob_gemm_lt_tune(const int64_t* shape) {
   return ob_lt_tune_shape(key_from_i64(shape).s);
 }
 
+// ob_gemm_lt_tune for a caller that can run the shape sliced with a slab of
+// slab_floats floats (what ob_layer_create does for a BLOCK's weight grads)
+extern "C" int ob_gemm_lt_tune_slab(const int64_t* shape,
+                                    int64_t slab_floats) {
+  if (!shape) return ob_fail("gemm_lt_tune_slab: null shape");
+  return ob_lt_tune_shape(key_from_i64(shape).s,
+                          slab_floats > 0 ? slab_floats : 0);
+}
+
 extern "C" int ob_gemm_lt_choice(const int64_t* shape, double* out,
                                  char* top1_name, char* chosen_name,
                                  int name_cap) {
@@ -677,6 +990,35 @@ extern "C" int ob_gemm_lt_choice(const int64_t* shape, double* out,
   if (chosen_name && name_cap > 0)
     snprintf(chosen_name, name_cap, "%s", c.chosen_name.c_str());
   return 0;
+}
+
+// The sliced side of a shape's table entry.  out[0] = entry found, out[1] =
+// the slice count the step runs (1: unsliced), out[2] = the batched problem's
+// solution index (-1 unsliced), out[3] = the fastest sliced pair's median
+// microseconds (matmul + fold; 0 if none was timed), out[4] = the
+// milliseconds the sliced candidates added to the shape's tuning time,
+// out[5] = that fastest pair's slice count.  Every sliced pair that was timed
+// goes to slices/index/us, fastest first; returns their number.
+extern "C" int ob_gemm_lt_slices(const int64_t* shape, double* out,
+                                 int32_t* slices, int32_t* index, double* us,
+                                 int cap) {
+  if (!shape || !out || (cap > 0 && (!slices || !index || !us))) return -1;
+  for (int i = 0; i < 6; i++) out[i] = 0;
+  std::lock_guard<std::mutex> lk(g_tab_mu);
+  auto it = g_tab.find(key_from_i64(shape));
+  if (it == g_tab.end()) return 0;
+  const LtChoice& c = it->second;
+  auto v = c.sliced;
+  std::stable_sort(v.begin(), v.end(),
+                   [](const LtChoice::Sliced& a, const LtChoice::Sliced& b) {
+                     return a.us < b.us;
+                   });
+  out[0] = 1, out[1] = c.tuned ? c.slices : 1;
+  out[2] = c.tuned ? c.slice_index : -1, out[3] = c.us_sliced;
+  out[4] = c.slice_ms, out[5] = v.empty() ? 1 : v[0].slices;
+  for (int i = 0; i < (int)v.size() && i < cap; i++)
+    slices[i] = v[i].slices, index[i] = v[i].index, us[i] = v[i].us;
+  return (int)v.size();
 }
 
 // the candidates the tuner timed for a shape, fastest first: solution index,

@@ -293,7 +293,15 @@ inline ob_lt_shape ob_lt_dw(int64_t actw, int64_t dyw, int64_t BS,
 }
 // tunes one shape if the choice table has no entry for it (host code, never
 // inside a step; a no-op with OB_LT_TUNE=0).  0, or 1 with ob_fail set.
-int ob_lt_tune_shape(const ob_lt_shape& s);
+// slab_floats > 0: the caller can run the shape sliced along K with a slab of
+// that many floats (ob_dw_slices.h), so the sliced forms are measured too.
+int ob_lt_tune_shape(const ob_lt_shape& s, int64_t slab_floats = 0);
+// a listed dw shape's call: gout += act^T dY, as the slice count of the
+// choice table says (1 without an entry, with OB_DW_SLICES=1, OB_LT_TUNE=0
+// and in deterministic mode); slab is scratch of slab_floats floats on the
+// caller's stream.  Returns as ob_gemm_lt.
+int ob_lt_dw_run(const ob_lt_shape& s, const void* act, const void* dY,
+                 float* gout, float* slab, int64_t slab_floats, void* stream);
 
 // ---------------------------------------------------------------------------
 // bf16 GEMM call (ob_gemm_bf16.hip): C = alpha * op(A) op(B) (+ bias)

@@ -437,8 +437,10 @@ static int layer_create(const ob_layer_desc* d, const ob_dropout_desc* drop,
   if (!no_blaslt()) {
     std::vector<ob_lt_shape> shapes;
     ob_layer_lt_list(d, l->p_resid > 0.f, &shapes);
+    // a BLOCK's weight grads may run sliced along K with WS_DW_A as the slab
+    const int64_t slab = d->kind == OB_KIND_BLOCK ? pl.ws[WS_DW_A] : 0;
     for (const ob_lt_shape& s : shapes)
-      if (ob_lt_tune_shape(s)) return 1;
+      if (ob_lt_tune_shape(s, s.tA ? slab : 0)) return 1;
   }
   g_layers_created++;
   *out = guard.release();
@@ -813,9 +815,12 @@ static int dw_bf16_ws(const ob_lt_shape& s, const __bf16* act,
   // direct TN via hipBLASLt with beta=1 accumulation into the fp32 flat
   // grads: no transpose materialization, no atomics (measured 694 TF on
   // the fc dW shape vs 436 for transpose + atomic NT)
+  // the 128x128 tiles of a block's dW outputs cover 36 to 144 of 256 CUs, so
+  // where the tuner measured it faster the call runs as K-slices into
+  // WS_DW_A (idle on this path) and a fold (ob_dw_slices.h)
   if (!no_blaslt()) {
-    const int r = ob_gemm_lt(s.tA, s.tB, s.M, s.N, s.K, 1.f, act, s.lda, dY,
-                             s.ldb, 1.f, gout, s.ldc, s.c_f32, stream);
+    const int r = ob_lt_dw_run(s, act, dY, gout, ws<float>(WS_DW_A),
+                               g_ws.size[WS_DW_A], stream);
     if (r >= 0) return r;
   }
   // gout[actw,dyw] += act^T dY, atomically, K = BS split to fill the chip

@@ -39,7 +39,10 @@ enum {
   WS_DY4,        // main, read by side until the join: MLP grads [BS, 4H]
   WS_FLASH_BWD,  // main: flash D [B*nh, S]; OB_FLASH_TR=0: Q^T|K^T|dO^T|D
   WS_FLASH_VT,   // fwd: V^T, OB_FLASH_TR=0 only
-  WS_DW_A,       // side: dW fallback's A^T (act^T; FINAL: dlogits^T), bf16
+  WS_DW_A,       // side: BLOCK: the fp32 slab [s, M, N] of a sliced dW call
+                 // (ob_dw_slices.h), or, when the library takes no part, the
+                 // dW fallback's A^T (act^T; FINAL: dlogits^T), bf16; a call
+                 // runs one of the two, so the buffer has one user at a time
   WS_DW_B,       // side: dW fallback's B^T (dY^T; FINAL: ln_f out^T), bf16
   WS_PD_FWD,     // fwd: Pd = drop(P), attention dropout without flash
   WS_PD_BWD,     // main: Pd regenerated, attention dropout without flash
