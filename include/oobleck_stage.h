@@ -96,7 +96,9 @@ typedef struct {
   float resid_pdrop;    /* BLOCK layers, sites 2 and 3 */
   float attn_pdrop;     /* BLOCK layers, site 1.  A flash-eligible layer draws
                            the masks inside the flash kernels
-                           (ob_flash_*_nt_drop_bf16); with OB_FLASH_DROP=0 or
+                           (ob_flash_*_nt_drop_bf16; at head_dim 128
+                           ob_flash_*_drop_hd128_bf16, only with
+                           OB_FLASH_HD128_DROP=1); with OB_FLASH_DROP=0 or
                            OB_FLASH_TR=0 in the environment, > 0 takes the
                            materialized-P attention path instead */
   int32_t layer_id;     /* 0 <= layer_id < 2^24 */
@@ -111,8 +113,9 @@ int ob_layer_create_ex(const ob_layer_desc* desc, const ob_dropout_desc* drop,
 /* 1 when the layer's attention runs the fused flash kernels (bf16 BLOCK,
  * n_embd % n_head == 0, head_dim 64 or 128, seq_len % 128 == 0; at head_dim
  * 64, for attn_pdrop > 0, neither OB_FLASH_DROP=0 nor OB_FLASH_TR=0; at
- * head_dim 128 attn_pdrop == 0 and neither OB_FLASH_TR=0 nor
- * OB_FLASH_HD128=0), 0 otherwise.  Host-only. */
+ * head_dim 128 neither OB_FLASH_TR=0 nor OB_FLASH_HD128=0 and, for
+ * attn_pdrop > 0, also OB_FLASH_HD128_DROP=1 (default 0) and not
+ * OB_FLASH_DROP=0), 0 otherwise.  Host-only. */
 int ob_layer_uses_flash(ob_layer_t l);
 /* The same decision for a description, before any layer exists: what
  * ob_layer_create_ex will take for `desc` with this attn_pdrop.  Host-only,
@@ -122,9 +125,9 @@ int ob_flash_eligible(const ob_layer_desc* desc, float attn_pdrop);
 /* The device memory ob_layer_create_ex takes for `desc` (drop may be null),
  * from the same table the create allocates by (DESIGN.md "Layer memory").
  * modes: bit 0 deterministic, 1 OB_BF16_FLASH, 2 OB_FLASH_TR, 3
- * OB_FLASH_DROP, 4 OB_FLASH_HD128 (a set bit = that switch on); -1 = this
- * process's.  Writes up to cap int64s and returns the field count (-1 on a
- * null argument).  Fields, in order: flash, side (needs the side stream),
+ * OB_FLASH_DROP, 4 OB_FLASH_HD128, 5 OB_FLASH_HD128_DROP (a set bit = that
+ * switch on); -1 = this process's.  Writes up to cap int64s and returns the
+ * field count (-1 on a null argument).  Fields, in order: flash, side (needs the side stream),
  * v_pad, slot_stride (floats of one stash slot), ids_count (int64s, all
  * slots), shadow_count (bf16 elements); the 15 stash regions' offsets within
  * a slot, then their lengths (floats; x, mean1, rstd1, ln1, qkv, p, attnm,
@@ -465,6 +468,21 @@ int ob_flash_bwd_nt_d_drop_bf16(const void* qkv, const void* O, const void* dO,
                                 int64_t H, int64_t nh, float scale,
                                 uint64_t seed, int32_t layer_id, uint64_t tick,
                                 float p, void* stream);
+/* The same two at head_dim 128 (H == 128 * nh; the two above keep refusing
+ * it): the same mask, LSE and backward definitions, the same checks, made
+ * before any launch; p == 0 launches the plain kernels.  The backward runs
+ * dq (forming D into D_ws) first, then dkdv; dbias_qkv may be null. */
+int ob_flash_fwd_drop_hd128_bf16(const void* qkv, void* O, void* lse,
+                                 int64_t B, int64_t Sq, int64_t H, int64_t nh,
+                                 float scale, uint64_t seed, int32_t layer_id,
+                                 uint64_t tick, float p, void* stream);
+int ob_flash_bwd_d_drop_hd128_bf16(const void* qkv, const void* O,
+                                   const void* dO, const void* lse,
+                                   void* D_ws, void* dqkv, void* dbias_qkv,
+                                   int64_t B, int64_t Sq, int64_t H,
+                                   int64_t nh, float scale, uint64_t seed,
+                                   int32_t layer_id, uint64_t tick, float p,
+                                   void* stream);
 /* Host-only queries of the block -> work mapping of the three kernels above
  * (no GPU call).  kind: 0 forward, 1 dq, 2 dkdv.
  * rows: unit = wave 0..3 (forward, dq) or wave pair 0..1 (dkdv) of `block`

@@ -190,6 +190,11 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.ob_flash_bwd_nt_d_drop_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp,
                                                 i64, i64, i64, i64, f32, u64,
                                                 i32, u64, f32, vp]
+    # the same two argument lists, head_dim 128
+    lib.ob_flash_fwd_drop_hd128_bf16.argtypes = (
+        lib.ob_flash_fwd_nt_drop_bf16.argtypes)
+    lib.ob_flash_bwd_d_drop_hd128_bf16.argtypes = (
+        lib.ob_flash_bwd_nt_d_drop_bf16.argtypes)
     # deterministic mode (include/oobleck_stage.h)
     lib.ob_set_deterministic.argtypes = [i32]
     lib.ob_deterministic.argtypes = []
@@ -332,6 +337,7 @@ LAYER_PLAN_NAMES = (
 # bits of ob_layer_plan_query's modes
 PLAN_DET, PLAN_BF16_FLASH, PLAN_FLASH_TR, PLAN_FLASH_DROP, PLAN_FLASH_HD128 = (
     1, 2, 4, 8, 16)
+PLAN_FLASH_HD128_DROP = 32  # OB_FLASH_HD128_DROP, off by default
 
 
 def layer_plan(desc: ObLayerDesc, drop: ObDropoutDesc | None = None,

@@ -127,45 +127,9 @@ __device__ __forceinline__ bf16x8 nt_tr_frag(const __bf16* tile, int lane,
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-// Attention dropout (kDrop instantiations).  The mask
-// is ob_philox.h's, site OB_DROP_ATTN: element e = (z*S + q)*S + kv of the
-// full [B*nh, S, S] square, word e & 3 of ob_drop_words(key, e >> 2), and
-// ob_drop_factor's rule (word >= thr keeps, kept values times key.scale).
-// No mask touches memory: a Philox call covers four consecutive, 4-aligned
-// kv of one q row, S % 4 == 0, and e < 2^34 (checked by the entries), so
-//   e >> 2 = (z*S + q) * (S/4) + (kv >> 2)   fits 32 bits.
-// The kernels keep the keep bits of a tile in one register and apply
-// `bit ? key.scale : 0` where ob_drop_factor would.  Only elements at or
-// below the diagonal ever reach a product that matters: masked P is 0
-// before the factor multiplies it.  The mask code is plain VALU (plus one
-// quad exchange in dkdv) under wave-uniform control and holds no
-// transposed read and no barrier.
-//
-// forward / dq orientation: a lane holds q = myq and, per 32-kv sub-tile u,
-// the kv rows kv0 + 32u + acc_row(r, kh): group g = r>>2 is the 4-aligned
-// run kv0 + 32u + 8g + 4kh, i.e. exactly one Philox call, counter
-// crow + 8u + 2g with crow = drop_crow(z, S, myq, kh) + kv0/4.  Bit 16u + r
-// = keep of sub-tile u, element r.  8 calls per lane and 64-kv tile, in a
-// rolled loop: unrolled, their temporaries push the kernels into scratch.
-__device__ __forceinline__ uint32_t drop_crow(int z, int Sq, int q, int kh) {
-  return (uint32_t)(z * Sq + q) * (uint32_t)(Sq >> 2) + (uint32_t)kh;
-}
-__device__ __forceinline__ uint32_t drop_bits_q(const ob_drop_key& key,
-                                                uint32_t crow) {
-  uint32_t bits = 0;
-#pragma unroll 1
-  for (int i = 0; i < 8; ++i) {  // i = 4u + g
-    const ob_philox4 w = ob_drop_words(key, crow + 2 * i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      bits |= (uint32_t)(w.w[j] >= key.thr) << (4 * i + j);
-  }
-  return bits;
-}
-__device__ __forceinline__ float drop_factor_bit(const ob_drop_key& key,
-                                                 uint32_t bits, int i) {
-  return ((bits >> i) & 1u) ? key.scale : 0.f;
-}
+// Attention dropout (kDrop instantiations): the mask
+// definition and drop_crow / drop_bits_q / drop_factor_bit are in
+// ob_flash_common.h, shared with the head_dim 128 kernels.
 
 // Forward: 4 waves x 32 q-rows = 128 q-rows per block; KVBLK = 64.
 //   * K and V tiles STAGED IN LDS, double-buffered, shared by the 4 waves

@@ -14,10 +14,25 @@
 // image below.  All three kernels are bound to 2 waves/SIMD (256 VGPRs);
 // none uses scratch (profiles/flash_hd128_resources.txt).
 //
-// Out of scope: attention dropout at head_dim 128 (ob_flash_*_nt_drop_bf16
-// keep rejecting it; such a layer takes the materialized route), transposed-
-// operand twins (torch is the reference: tests/test_gpu_flash_hd128.py),
-// head_dim 80/96, fp32 flash.
+// Attention dropout (the mask definition and helpers
+// are ob_flash_common.h's, the hd-64 kernels').  Three `_drop` kernels
+// behind entries of their own, ob_flash_fwd_drop_hd128_bf16 and
+// ob_flash_bwd_d_drop_hd128_bf16 (ob_flash_*_nt_drop_bf16 keep rejecting
+// head_dim 128).  They are separate kernels, not template <bool kDrop>
+// instantiations, because they carry a function attribute the plain ones
+// must not get (OB_DROP_KERNEL below) and the plain ones keep their
+// argument lists.  The forward and dQ bodies are forceinline device
+// templates on kDrop with two thin __global__ wrappers each (body<false>
+// under the name and signature the kernel always had, body<true> taking the
+// ob_drop_key by value): one definition of the arithmetic, and the plain
+// wrappers compile to the resources they had.  The dK/dV kernel, one
+// register under the limit, did not (254 VGPRs for 255), so it is left
+// untouched and its dropout variant is a copy.  Where each kernel draws the
+// mask is in its header; the resources of all of them, with and without
+// the attribute, are profiles/flash_hd128_drop_resources.txt.
+//
+// Out of scope: transposed-operand twins (torch is the reference:
+// tests/test_gpu_flash_hd128.py), head_dim 80/96, fp32 flash.
 //
 // LDS image of a [rows][128] bf16 tile (256-byte rows = one full sweep of
 // the 64 banks, sixteen 16-byte chunks):
@@ -45,6 +60,17 @@
 #include <cmath>
 
 static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+// The `_drop` kernels are compiled without packed fp32 VALU ops.  This is
+// part of their register budget, not decoration: with the ops allowed the
+// compiler pairs the fp32 work of the P loops, the 64-bit operand pairs
+// need aligned register pairs, and the dK/dV variant goes from 253 VGPRs
+// and no scratch to 256 VGPRs and 76 B/lane of scratch, the forward from
+// 192 VGPRs to 225 (dQ: 242 either way).  What un-pairing costs in time was
+// measured on the plain kernels, which run either way: DESIGN.md §8 item
+// 20.  Remove the attribute only together with a re-cut of dK/dV role 0 or
+// with __launch_bounds__(256, 1) on that kernel, and re-take the table.
+#define OB_DROP_KERNEL __attribute__((target("no-packed-fp32-ops")))
 
 __device__ __forceinline__ int hd_key(int row) {
   return ((row & 3) << 2) | ((row >> 2) & 3);
@@ -76,9 +102,17 @@ __device__ __forceinline__ bf16x8 hd_tr_frag(const __bf16* tile, int lane,
 // tile).  Q is 8 fragments, O four accumulators; the PV B fragments are
 // read one d quarter at a time (16 VGPRs per k-step, not 64 for a tile).
 // LDS: 2 x (16 KB K + 16 KB V) + bcast = 64.5 KB, two blocks per CU.
-__global__ __launch_bounds__(256, 2) void k_flash_fwd_hd128(
+// kDrop: m, l and the stored LSE come from the undropped P.  The tile's 32
+// keep bits are drawn at the top of the iteration, while only Q, O and the
+// row state are live (before the staging loads and the S chains take their
+// registers), and cost one register from there on; each k-step's 8 P values
+// take their factor in fp32 just before bf_dance packs them, ahead of that
+// k-step's B fragment reads.
+template <bool kDrop>
+__device__ __forceinline__ void hd128_fwd_body(
     const __bf16* __restrict__ qkv, __bf16* __restrict__ Obase,
-    float* __restrict__ lse, int Sq, int H, int nh, int Z, float scale) {
+    float* __restrict__ lse, int Sq, int H, int nh, int Z, float scale,
+    const ob_drop_key& key) {
   __shared__ __attribute__((aligned(16))) __bf16 kbuf[2][64 * 128];
   __shared__ __attribute__((aligned(16))) __bf16 vbuf[2][64 * 128];
   __shared__ float bcast[128];
@@ -134,6 +168,10 @@ __global__ __launch_bounds__(256, 2) void k_flash_fwd_hd128(
   float m = -INFINITY, l = 0.f;
   for (int kvt = 0; kvt < ntiles; ++kvt) {
     const int kv0 = kvt * 64;
+    [[maybe_unused]] uint32_t keep = 0;  // bit 16u + r, as drop_bits_q
+    if constexpr (kDrop)
+      if (kvt < mytiles)  // wave-uniform
+        keep = drop_bits_q(key, drop_crow(z, Sq, myq, kh) + (kv0 >> 2));
     if (kvt + 1 < ntiles) stage((kvt + 1) & 1, kv0 + 64);
     const bool active = kvt < mytiles;  // kv0 <= q0 + 31, wave-uniform
     if (active) {
@@ -201,6 +239,11 @@ __global__ __launch_bounds__(256, 2) void k_flash_fwd_hd128(
       l += psum;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
+        if constexpr (kDrop) {
+#pragma unroll
+          for (int r = 8 * t; r < 8 * t + 8; ++r)
+            sv[r] *= drop_factor_bit(key, keep, r);
+        }
         const bf16x8 pa = bf_dance(sv + t * 8);
         // B[k = kv 16t+8kh..+7][n = d]: columns of the row-major V tile
 #pragma unroll
@@ -226,6 +269,18 @@ __global__ __launch_bounds__(256, 2) void k_flash_fwd_hd128(
     for (int d = 0; d < 4; ++d)
       Op[(int64_t)(q0 + row) * H + 32 * d + il] = (__bf16)(o[d][r] * inv);
   }
+}
+__global__ __launch_bounds__(256, 2) void k_flash_fwd_hd128(
+    const __bf16* __restrict__ qkv, __bf16* __restrict__ Obase,
+    float* __restrict__ lse, int Sq, int H, int nh, int Z, float scale) {
+  hd128_fwd_body<false>(qkv, Obase, lse, Sq, H, nh, Z, scale, ob_drop_key{});
+}
+__global__ OB_DROP_KERNEL __launch_bounds__(256, 2) void
+k_flash_fwd_hd128_drop(const __bf16* __restrict__ qkv,
+                       __bf16* __restrict__ Obase, float* __restrict__ lse,
+                       int Sq, int H, int nh, int Z, float scale,
+                       ob_drop_key key) {
+  hd128_fwd_body<true>(qkv, Obase, lse, Sq, H, nh, Z, scale, key);
 }
 
 // dK/dV: k_flash_bwd_dkdv_nt's split-duty wave pairs (role 0: K resident,
@@ -390,6 +445,223 @@ __global__ __launch_bounds__(256, 2) void k_flash_bwd_dkdv_hd128(
   }
 }
 
+// dK/dV with attention dropout: k_flash_bwd_dkdv_hd128 above, line for
+// line, plus the mask.  A copy, not a shared body: the plain kernel sits
+// one register under the 256 limit, and reached through an inlined body
+// template it did not reproduce its allocation (254 VGPRs, not 255), so
+// its text stays untouched.  A change to one of the two belongs in the
+// other.
+// dV accumulates Pd^T dO, dK accumulates dS^T Q with
+// dS = P * (factor*dP - D).  Role 0 draws the mask with the hd-64 kernel's
+// quad-shared draw (quad lane j makes the 4 Philox calls of rows 4g + j and
+// the quad exchanges the packed bits), at the top of the iteration: only
+// the resident fragments and the accumulators are live there, the 8 B
+// fragments are not yet read.  It hands the mask to role 1 as the sign bit
+// of the fp32 P it writes to xch; role 1 draws nothing.
+// Register budget: see OB_DROP_KERNEL at the top of the file.  This kernel
+// fits 2 waves/SIMD only with the attribute.
+__device__ __forceinline__ void hd128_dkdv_drop_body(
+    const __bf16* __restrict__ qkv, const __bf16* __restrict__ dO,
+    const float* __restrict__ lse, const float* __restrict__ D,
+    __bf16* __restrict__ dqkv, float* __restrict__ dbias, int Sq, int H,
+    int nh, int Z, float scale, const ob_drop_key& key) {
+  __shared__ float xch[2][2][32 * 32];  // [buffer][pair][P tile]
+  __shared__ __attribute__((aligned(16))) __bf16 qbuf[2][32 * 128];
+  __shared__ __attribute__((aligned(16))) __bf16 obuf[2][32 * 128];
+  __shared__ float red[4 * 128];
+  int blk, z;
+  if (!ob_fold_id(blockIdx.x, ob_fold_kv_nblk(Sq), Z, &blk, &z))
+    return;  // block-uniform: grid padding
+  const int b = z / nh, h = z % nh;
+  const int64_t base = (int64_t)b * Sq * 3 * H + h * 128;
+  const __bf16* Qp = qkv + base;
+  const __bf16* Kp = Qp + H;
+  const __bf16* Vp = Qp + 2 * H;
+  const __bf16* dOp = dO + (int64_t)b * Sq * H + h * 128;
+  const float* lsep = lse + (int64_t)z * Sq;
+  const float* Dp = D + (int64_t)z * Sq;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int w = tid >> 6;
+  const int pair = w >> 1, role = w & 1;
+  const int il = lane & 31, kh = lane >> 5;
+  const int kv0 = ob_fold_kv_row0(Sq, blk, pair);
+  const int mykv = kv0 + il;
+  const int myqt0 = ob_fold_kv_pair_first(kv0);
+
+  const __bf16* KV = role ? Vp : Kp;
+  bf16x8 of[8];
+#pragma unroll
+  for (int s = 0; s < 8; ++s)
+    of[s] = *reinterpret_cast<const bf16x8*>(
+        KV + (int64_t)mykv * 3 * H + s * 16 + kh * 8);
+
+  // staging: thread covers chunk tid&15 of rows tid>>4 and (tid>>4) + 16
+  const int srow = tid >> 4, schunk = tid & 15;
+  const int so = hd_off(srow, schunk);
+  auto stage = [&](int buf, int q0s) {
+    bf16x8 qr[2], dr[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      qr[i] = *reinterpret_cast<const bf16x8*>(
+          Qp + (int64_t)(q0s + srow + 16 * i) * 3 * H + schunk * 8);
+      dr[i] = *reinterpret_cast<const bf16x8*>(
+          dOp + (int64_t)(q0s + srow + 16 * i) * H + schunk * 8);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      *reinterpret_cast<bf16x8*>(&qbuf[buf][so + 16 * 128 * i]) = qr[i];
+      *reinterpret_cast<bf16x8*>(&obuf[buf][so + 16 * 128 * i]) = dr[i];
+    }
+  };
+
+  f32x16 acc[4] = {};  // role 0: dV d quarters; role 1: dK d quarters
+  const int nqt = Sq / 32;
+  const int qt0 = ob_fold_kv_block_first(blk);  // block-uniform
+  stage(qt0 & 1, qt0 * 32);
+  __syncthreads();
+
+  for (int qt = qt0; qt < nqt; ++qt) {
+    const int q0 = qt * 32;
+    // bit r: keep of element r (q row q0 + acc_row(r, kh), column mykv)
+    uint32_t keep = 0;
+    {
+      if (role == 0 && qt >= myqt0) {  // wave-uniform
+        // Philox counter of q row q0 + 4*kh at this lane's kv quad
+        const uint32_t sq4 = (uint32_t)(Sq >> 2);
+        const uint32_t c0 = (uint32_t)(z * Sq + q0 + 4 * kh) * sq4 +
+                            (uint32_t)(mykv >> 2);
+        uint32_t mine = 0;  // rows r = 4g + (il & 3): bit 4g + word
+#pragma unroll 1
+        for (int g = 0; g < 4; ++g) {
+          const ob_philox4 w4 =
+              ob_drop_words(key, c0 + (uint32_t)((il & 3) + 8 * g) * sq4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            mine |= (uint32_t)(w4.w[j] >= key.thr) << (4 * g + j);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          // quad lane j drew rows 4g + j; take this lane's word of each
+          const uint32_t theirs =
+              (uint32_t)__shfl((int)mine, (lane & ~3) | j, 64) >> (il & 3);
+#pragma unroll
+          for (int g = 0; g < 4; ++g)
+            keep |= ((theirs >> (4 * g)) & 1u) << (4 * g + j);
+        }
+      }
+    }
+    if (qt + 1 < nqt) stage((qt + 1) & 1, q0 + 32);
+    // wave-uniform: pair 1 idles (staging and the barrier only) until the
+    // loop reaches its diagonal, q0 + 31 >= kv0.  Each wave meets exactly
+    // one barrier per iteration on either side of the branch.
+    if (qt < myqt0) {
+      __syncthreads();
+      continue;
+    }
+    // own tile's A image, and the B image: role 0 multiplies P^T by dO,
+    // role 1 dS^T by Q
+    const __bf16* ab = role ? obuf[qt & 1] : qbuf[qt & 1];
+    const __bf16* bb = role ? qbuf[qt & 1] : obuf[qt & 1];
+    // B-operands early (before the barrier): 4 d quarters, k = q rows
+    bf16x8 bf[2][4];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+        bf[t][d] = hd_tr_frag(bb, lane, 16 * t + kh * 8, d);
+    // own tile: S (role 0, A = Q rows) or dP (role 1, A = dO rows)
+    f32x16 own = {};
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const int ch = s * 2 + kh;
+      const bf16x8 af =
+          *reinterpret_cast<const bf16x8*>(&ab[hd_off(il, ch)]);
+      own = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, of[s], own, 0, 0,
+                                                    0);
+    }
+    float pv[16];
+    float* ptile = xch[qt & 1][pair];
+    if (role == 0) {
+      const float lse_t = lsep[q0 + il];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int qoff = acc_row(r, kh);
+        const bool ok = q0 + qoff >= mykv;
+        const float lse_q = __shfl(lse_t, qoff, 64);
+        pv[r] = ok ? __expf(own[r] * scale - lse_q) : 0.f;
+        const bool kept = (keep >> r) & 1u;
+        ptile[qoff * 32 + il] = kept ? pv[r] : -pv[r];
+        pv[r] = kept ? pv[r] * key.scale : 0.f;
+      }
+    }
+    __syncthreads();
+    if (role == 1) {
+      const float d_t = Dp[q0 + il];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int qoff = acc_row(r, kh);
+        const float d_q = __shfl(d_t, qoff, 64);
+        // dS = P * (factor*dP - D): |x| is P, a set sign bit says dropped
+        const float x = ptile[qoff * 32 + il];
+        const float f = __builtin_signbit(x) ? 0.f : key.scale;
+        pv[r] = __builtin_fabsf(x) * (f * own[r] - d_q);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const bf16x8 a = bf_dance(pv + t * 8);
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+        acc[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bf[t][d], acc[d],
+                                                         0, 0, 0);
+    }
+  }
+
+  __bf16* outp = dqkv + base + (role ? H : 2 * H);  // dK or dV slice
+  const float os = role ? scale : 1.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int kv = kv0 + acc_row(r, kh);
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+      outp[(int64_t)kv * 3 * H + 32 * d + il] = (__bf16)(os * acc[d][r]);
+  }
+  if (dbias) {  // kernel-uniform
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      float c = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) c += os * acc[d][r];
+      c += __shfl_xor(c, 32, 64);
+      if (kh == 0) red[w * 128 + 32 * d + il] = c;
+    }
+    __syncthreads();
+    {
+      // waves 0/2 hold dV (role 0), waves 1/3 dK (role 1)
+      const int rl = tid >> 7, c = tid & 127;
+      atomicAdd(dbias + (rl ? H : 2 * H) + h * 128 + c,
+                red[rl * 128 + c] + red[(2 + rl) * 128 + c]);
+    }
+  }
+}
+// The kernel is a wrapper, as for the forward and dQ: written straight into
+// an attributed __global__, the `stage` lambda (which does not carry the
+// attribute) is inlined too late for its closure to leave memory, 96 B/lane
+// of scratch.
+__global__ OB_DROP_KERNEL __launch_bounds__(256, 2) void
+k_flash_bwd_dkdv_hd128_drop(const __bf16* __restrict__ qkv,
+                            const __bf16* __restrict__ dO,
+                            const float* __restrict__ lse,
+                            const float* __restrict__ D,
+                            __bf16* __restrict__ dqkv,
+                            float* __restrict__ dbias, int Sq, int H, int nh,
+                            int Z, float scale, ob_drop_key key) {
+  hd128_dkdv_drop_body(qkv, dO, lse, D, dqkv, dbias, Sq, H, nh, Z, scale,
+                       key);
+}
+
 // dQ: k_flash_bwd_dq_nt's structure (the forward's blocks and K/V staging;
 // S^T, P^T, dP^T, dS^T, dQ += dS K with K^T read column-wise from the K
 // tile).  With Q and dO resident (16 fragments) and 4 dQ accumulators the
@@ -401,13 +673,16 @@ __global__ __launch_bounds__(256, 2) void k_flash_bwd_dkdv_hd128(
 // fragments and O loaded in the same layout, used, and written to Dout for
 // the dkdv launch that follows.
 // LDS: 2 x (16 KB K + 16 KB V) + red 2 KB = 66 KB.
-template <bool kFormD>
-__global__ __launch_bounds__(256, 2) void k_flash_bwd_dq_hd128(
+// kDrop: D is unchanged; dS = P * (factor*dP - D) with the undropped P.  A
+// sub-tile needs only its own 16 keep bits (4 Philox calls), drawn just
+// before its S and dP chains: no tile mask lives across the tile.
+template <bool kFormD, bool kDrop>
+__device__ __forceinline__ void hd128_dq_body(
     const __bf16* __restrict__ qkv, const __bf16* __restrict__ dO,
     const float* __restrict__ lse, const float* __restrict__ D,
     const __bf16* __restrict__ O, float* __restrict__ Dout,
     __bf16* __restrict__ dqkv, float* __restrict__ dbias, int Sq, int H,
-    int nh, int Z, float scale) {
+    int nh, int Z, float scale, const ob_drop_key& key) {
   __shared__ __attribute__((aligned(16))) __bf16 kbuf[2][64 * 128];
   __shared__ __attribute__((aligned(16))) __bf16 vbuf[2][64 * 128];
   __shared__ float red[4 * 128];
@@ -444,6 +719,7 @@ __global__ __launch_bounds__(256, 2) void k_flash_bwd_dq_hd128(
     const __bf16* Orow =
         O + (int64_t)b * Sq * H + h * 128 + (int64_t)myq * H;
     float part = 0.f;
+    [[maybe_unused]] float cs[8];
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
       const bf16x8 ov =
@@ -451,8 +727,17 @@ __global__ __launch_bounds__(256, 2) void k_flash_bwd_dq_hd128(
       float c = 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) c += bf2f(ov[j]) * bf2f(df[s][j]);
-      part += c;
+      if constexpr (kDrop)
+        cs[s] = c;
+      else
+        part += c;
     }
+    // kDrop: k_flash_dsum<128>'s order (cs[s] = chunk 2s + kh; its shuffle
+    // tree adds chunks 8, 4, 2, then 1 apart), so D is bit-identical to that
+    // kernel's as at head_dim 64; the plain kernel keeps the sum it had
+    if constexpr (kDrop)
+      part = ((cs[0] + cs[4]) + (cs[2] + cs[6])) +
+             ((cs[1] + cs[5]) + (cs[3] + cs[7]));
     myD = part + __shfl_xor(part, 32, 64);
     if (kh == 0) Dout[(int64_t)z * Sq + myq] = myD;
   } else {
@@ -493,6 +778,10 @@ __global__ __launch_bounds__(256, 2) void k_flash_bwd_dq_hd128(
       const __bf16* vb = vbuf[kvt & 1];
 #pragma unroll
       for (int u = 0; u < 2; ++u) {  // 32-row kv sub-tiles, in turn
+        [[maybe_unused]] uint32_t keep = 0;  // bit r of this sub-tile
+        if constexpr (kDrop)
+          keep = drop_bits_q<4>(
+              key, drop_crow(z, Sq, myq, kh) + (kv0 >> 2) + 8 * u);
         f32x16 sa = {}, pa = {};
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
@@ -512,7 +801,11 @@ __global__ __launch_bounds__(256, 2) void k_flash_bwd_dq_hd128(
           const int kv = kv0 + 32 * u + acc_row(r, kh);
           const bool ok = kv <= myq;
           const float p = ok ? __expf(sa[r] * scale - mylse) : 0.f;
-          dsv[r] = ok ? p * (pa[r] - myD) : 0.f;
+          if constexpr (kDrop)
+            dsv[r] = ok ? p * (drop_factor_bit(key, keep, r) * pa[r] - myD)
+                        : 0.f;
+          else
+            dsv[r] = ok ? p * (pa[r] - myD) : 0.f;
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
@@ -553,6 +846,28 @@ __global__ __launch_bounds__(256, 2) void k_flash_bwd_dq_hd128(
                                            (red[256 + tid] + red[384 + tid]));
   }
 }
+template <bool kFormD>
+__global__ __launch_bounds__(256, 2) void k_flash_bwd_dq_hd128(
+    const __bf16* __restrict__ qkv, const __bf16* __restrict__ dO,
+    const float* __restrict__ lse, const float* __restrict__ D,
+    const __bf16* __restrict__ O, float* __restrict__ Dout,
+    __bf16* __restrict__ dqkv, float* __restrict__ dbias, int Sq, int H,
+    int nh, int Z, float scale) {
+  hd128_dq_body<kFormD, false>(qkv, dO, lse, D, O, Dout, dqkv, dbias, Sq, H,
+                               nh, Z, scale, ob_drop_key{});
+}
+// always forms D: the drop entry is the `_d` backward
+__global__ OB_DROP_KERNEL __launch_bounds__(256, 2) void
+k_flash_bwd_dq_hd128_drop(const __bf16* __restrict__ qkv,
+                          const __bf16* __restrict__ dO,
+                          const float* __restrict__ lse,
+                          const __bf16* __restrict__ O,
+                          float* __restrict__ Dout, __bf16* __restrict__ dqkv,
+                          float* __restrict__ dbias, int Sq, int H, int nh,
+                          int Z, float scale, ob_drop_key key) {
+  hd128_dq_body<true, true>(qkv, dO, lse, nullptr, O, Dout, dqkv, dbias, Sq,
+                            H, nh, Z, scale, key);
+}
 
 int ob_flash_hd128_fwd(const void* qkv, void* O, void* lse, int64_t B,
                        int64_t Sq, int64_t H, int64_t nh, float scale,
@@ -589,6 +904,69 @@ int ob_flash_hd128_bwd(const void* qkv, const void* O, const void* dO,
       (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse,
       (const float*)D, (__bf16*)dqkv, (float*)dbias_qkv, (int)Sq, (int)H,
       (int)nh, Z, scale);
+  OB_LAUNCH_CHECK();
+  return 0;
+}
+
+// argument checks shared by the two dropout entries, made before any launch
+static int drop_hd128_args_ok(const char* who, int64_t B, int64_t Sq,
+                              int64_t H, int64_t nh, float p) {
+  if (nh <= 0 || H % nh || H / nh != 128)
+    return ob_fail("%s: head_dim must be 128", who);
+  if (Sq <= 0 || Sq % 128)
+    return ob_fail("%s: S must be a multiple of 128", who);
+  if (!ob_drop_p_ok(p)) return ob_fail("%s: p must be in [0,1)", who);
+  if (B <= 0 || B * nh * Sq * Sq > ((int64_t)1 << 34))
+    return ob_fail("%s: B*nh*S*S exceeds the 2^34 mask elements", who);
+  return 0;
+}
+
+// ob_flash_fwd_nt_bf16 at head_dim 128 with attention dropout (site
+// OB_DROP_ATTN) applied to P before PV; p == 0 is the plain entry.
+extern "C" int ob_flash_fwd_drop_hd128_bf16(const void* qkv, void* O,
+                                            void* lse, int64_t B, int64_t Sq,
+                                            int64_t H, int64_t nh,
+                                            float scale, uint64_t seed,
+                                            int32_t layer_id, uint64_t tick,
+                                            float p, void* stream) {
+  if (drop_hd128_args_ok("flash_fwd_drop_hd128", B, Sq, H, nh, p)) return 1;
+  if (p == 0.f)
+    return ob_flash_fwd_nt_bf16(qkv, O, lse, B, Sq, H, nh, scale, stream);
+  const int Z = (int)(B * nh);
+  k_flash_fwd_hd128_drop<<<ob_fold_grid(ob_fold_q_nblk((int)Sq), Z), 256, 0,
+                           S(stream)>>>(
+      (const __bf16*)qkv, (__bf16*)O, (float*)lse, (int)Sq, (int)H, (int)nh,
+      Z, scale, ob_drop_make_key(seed, layer_id, OB_DROP_ATTN, tick, p));
+  OB_LAUNCH_CHECK();
+  return 0;
+}
+
+// ob_flash_bwd_nt_d_bf16 at head_dim 128 for a forward that ran
+// ob_flash_fwd_drop_hd128_bf16 with the same key: dq first (forms D from O
+// and dO into D_ws), then dkdv; p == 0 is the plain entry.
+extern "C" int ob_flash_bwd_d_drop_hd128_bf16(
+    const void* qkv, const void* O, const void* dO, const void* lse,
+    void* D_ws, void* dqkv, void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
+    int64_t nh, float scale, uint64_t seed, int32_t layer_id, uint64_t tick,
+    float p, void* stream) {
+  if (drop_hd128_args_ok("flash_bwd_d_drop_hd128", B, Sq, H, nh, p)) return 1;
+  if (p == 0.f)
+    return ob_flash_bwd_nt_d_bf16(qkv, O, dO, lse, D_ws, dqkv, dbias_qkv, B,
+                                  Sq, H, nh, scale, stream);
+  const ob_drop_key key =
+      ob_drop_make_key(seed, layer_id, OB_DROP_ATTN, tick, p);
+  const int Z = (int)(B * nh);
+  k_flash_bwd_dq_hd128_drop<<<ob_fold_grid(ob_fold_q_nblk((int)Sq), Z), 256,
+                              0, S(stream)>>>(
+      (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse,
+      (const __bf16*)O, (float*)D_ws, (__bf16*)dqkv, (float*)dbias_qkv,
+      (int)Sq, (int)H, (int)nh, Z, scale, key);
+  OB_LAUNCH_CHECK();
+  k_flash_bwd_dkdv_hd128_drop<<<ob_fold_grid(ob_fold_kv_nblk((int)Sq), Z),
+                                256, 0, S(stream)>>>(
+      (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse,
+      (const float*)D_ws, (__bf16*)dqkv, (float*)dbias_qkv, (int)Sq, (int)H,
+      (int)nh, Z, scale, key);
   OB_LAUNCH_CHECK();
   return 0;
 }

@@ -299,17 +299,21 @@ static bool no_blaslt() {
 // This process's modes.  OB_BF16_FLASH=0 keeps every layer on the
 // materialized-P path; OB_FLASH_DROP=0 sends attn_pdrop > 0 there, and
 // OB_FLASH_HD128=0 head_dim 128, as before those kernels existed
-// (ob_flash_*_nt_drop_bf16, ob_flash_hd128_bf16.hip).  All read once.
+// (ob_flash_*_nt_drop_bf16, ob_flash_hd128_bf16.hip).
+// OB_FLASH_HD128_DROP=1 (default 0) lets a head_dim 128 layer with
+// attn_pdrop > 0 take the flash kernels' dropout variants
+// (ob_flash_*_drop_hd128_bf16) instead of that path.  All read once.
 static ob_layer_modes process_modes() {
   static const bool fl = ob_env_flag("OB_BF16_FLASH", true),
                     drop = ob_env_flag("OB_FLASH_DROP", true),
-                    hd128 = ob_env_flag("OB_FLASH_HD128", true);
-  return {ob_deterministic() != 0, fl, flash_tr(), drop, hd128};
+                    hd128 = ob_env_flag("OB_FLASH_HD128", true),
+                    hd128_drop = ob_env_flag("OB_FLASH_HD128_DROP", false);
+  return {ob_deterministic() != 0, fl, flash_tr(), drop, hd128, hd128_drop};
 }
 static ob_layer_modes modes_of_bits(int bits) {
   if (bits < 0) return process_modes();
   return {(bits & 1) != 0, (bits & 2) != 0, (bits & 4) != 0, (bits & 8) != 0,
-          (bits & 16) != 0};
+          (bits & 16) != 0, (bits & 32) != 0};
 }
 
 // the decision ob_layer_create_ex takes for `d` with this attn_pdrop; host
@@ -870,11 +874,12 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
     // materialized-P path keeps P)
     if (dA) {
       // attention dropout inside the kernel: masks of this slot's tick
+      const auto fwd_drop = hd == 128 ? ob_flash_fwd_drop_hd128_bf16
+                                      : ob_flash_fwd_nt_drop_bf16;
       if (OB_PROF(OB_PF_FLASH_FWD, stream,
-                  ob_flash_fwd_nt_drop_bf16(s.qkv, s.am, s.lseP, B, Sq, H, nh,
-                                            1.f / sqrtf((float)hd), l->seed,
-                                            l->layer_id, l->slot_tick[slot],
-                                            l->p_attn, stream)))
+                  fwd_drop(s.qkv, s.am, s.lseP, B, Sq, H, nh,
+                           1.f / sqrtf((float)hd), l->seed, l->layer_id,
+                           l->slot_tick[slot], l->p_attn, stream)))
         return 1;
     } else if (OB_PROF(OB_PF_FLASH_FWD, stream,
                        ob_flash_fwd_nt_bf16(s.qkv, s.am, s.lseP, B, Sq, H, nh,
@@ -1088,12 +1093,12 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     float* const dbq = det ? nullptr : g + bp.b_qkv;
     if (dA) {
       // regenerates the masks the forward of this slot drew
+      const auto bwd_drop = hd == 128 ? ob_flash_bwd_d_drop_hd128_bf16
+                                      : ob_flash_bwd_nt_d_drop_bf16;
       if (OB_PROF(OB_PF_FLASH_BWD, stream,
-                  ob_flash_bwd_nt_d_drop_bf16(s.qkv, s.am, w.DATT, s.lseP, w.D,
-                                              w.DQKV, dbq, B, Sq, H, nh, scale,
-                                              l->seed, l->layer_id,
-                                              l->slot_tick[slot], l->p_attn,
-                                              stream)))
+                  bwd_drop(s.qkv, s.am, w.DATT, s.lseP, w.D, w.DQKV, dbq, B,
+                           Sq, H, nh, scale, l->seed, l->layer_id,
+                           l->slot_tick[slot], l->p_attn, stream)))
         return 1;
     } else if (OB_PROF(OB_PF_FLASH_BWD, stream,
                        ob_flash_bwd_nt_d_bf16(s.qkv, s.am, w.DATT, s.lseP, w.D,

@@ -57,6 +57,7 @@ enum {
 // the process switches a plan depends on
 struct ob_layer_modes {
   bool det, bf16_flash, flash_tr, flash_drop, flash_hd128;
+  bool flash_hd128_drop;  // OB_FLASH_HD128_DROP, off by default
 };
 
 struct ob_layer_plan {
@@ -82,8 +83,9 @@ inline int64_t ob_v_pad(int64_t V) { return (V + 255) / 256 * 256; }
 
 // flash applies to bf16 BLOCK layers with n_embd % n_head == 0, head_dim 64
 // (GPT-2 small and XL) or 128 (the GPT-3 sizes from 1.3B up) and S % 128 ==
-// 0.  head_dim 128 has production kernels only: no OB_FLASH_TR=0 twins and
-// no dropout variant; at head_dim 64 only the production kernels have one.
+// 0.  head_dim 128 has production kernels only (no OB_FLASH_TR=0 twins);
+// only the production kernels have dropout variants, and the head_dim 128
+// ones are taken only with flash_hd128_drop on.
 inline bool ob_plan_flash(const ob_layer_desc& d, float p_attn,
                           const ob_layer_modes& m) {
   if (p_attn > 0.f && !(m.flash_tr && m.flash_drop)) return false;
@@ -92,7 +94,9 @@ inline bool ob_plan_flash(const ob_layer_desc& d, float p_attn,
       d.seq_len % 128)
     return false;
   const int64_t hd = d.n_embd / d.n_head;
-  if (hd == 128) return p_attn == 0.f && m.flash_tr && m.flash_hd128;
+  if (hd == 128)
+    return m.flash_tr && m.flash_hd128 &&
+           (p_attn == 0.f || m.flash_hd128_drop);  // > 0: flash_drop is on
   return hd == 64;
 }
 

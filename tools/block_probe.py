@@ -4,7 +4,9 @@
 # layer holds on the device.  Device events around each window; the inputs
 # rotate over --rotate buffers so a window does not re-read what the last
 # call left in the caches.  The environment switches (OB_FLASH_HD128, ...)
-# are read once per process, so an A/B is two processes.
+# are read once per process, so an A/B is two processes.  --attn-pdrop P
+# creates the layer with attention dropout (OB_FLASH_HD128_DROP=1 keeps a
+# head_dim 128 layer on the flash route then).
 #
 #   python tools/block_probe.py --n-embd 4096 --n-head 32 --batch 2 --seq 1024
 import argparse
@@ -29,6 +31,7 @@ ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--reps", type=int, default=10, help="calls per window")
 ap.add_argument("--windows", type=int, default=5)
 ap.add_argument("--rotate", type=int, default=4, help="input buffer sets")
+ap.add_argument("--attn-pdrop", type=float, default=0.0, metavar="P")
 args = ap.parse_args()
 
 if not torch.cuda.is_available():
@@ -39,7 +42,10 @@ cfg = ModelConfig(n_embd=H, n_head=nh, n_layer=1, n_positions=max(S, 128),
                   vocab_size=304)
 torch.cuda.synchronize()
 free0 = torch.cuda.mem_get_info()[0]
-layer = Layer(1, cfg, B, S, args.slots, DEV, dtype="bf16")
+drop = {} if not args.attn_pdrop else dict(
+    embd_pdrop=0.0, resid_pdrop=0.0, attn_pdrop=args.attn_pdrop,
+    dropout_seed=7)
+layer = Layer(1, cfg, B, S, args.slots, DEV, dtype="bf16", **drop)
 torch.cuda.synchronize()
 held = free0 - torch.cuda.mem_get_info()[0]
 
@@ -79,6 +85,7 @@ for _ in range(args.windows):
     ms.append(st.elapsed_time(en) / args.reps)
 print(json.dumps({
     "n_embd": H, "n_head": nh, "batch": B, "seq": S, "slots": args.slots,
+    "attn_pdrop": args.attn_pdrop,
     "uses_flash": layer.uses_flash,
     "ms_fwd_bwd_median": round(statistics.median(ms), 4),
     "ms_fwd_bwd_min": round(min(ms), 4), "ms_fwd_bwd_max": round(max(ms), 4),

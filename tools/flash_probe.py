@@ -13,7 +13,10 @@
 # instead (there are no transposed-operand twins at 128), at --shape B,nh,S,
 # and prints TF next to the microseconds: causal FLOPs, 2*B*nh*S*S*hd for
 # the forward (2 GEMMs over half the square) and 5*B*nh*S*S*hd for the
-# backward (5 GEMMs).  The default, --head-dim 64, prints what it always did.
+# backward (5 GEMMs).  With --attn-pdrop P it adds the head_dim 128 dropout
+# entries (ob_flash_fwd_drop_hd128_bf16 / ob_flash_bwd_d_drop_hd128_bf16)
+# and their ratio to the plain rows.  The default, --head-dim 64, prints what
+# it always did.
 import argparse
 import ctypes
 import pathlib
@@ -138,14 +141,20 @@ def bwd_new_d(bias=None):
 DROP_KEY = ((0xDEADBEEF << 32) | 0x1234567, 5, (1 << 32) + 3)
 
 
+fwd_drop_entry, bwd_drop_entry = (
+    (ext.ob_flash_fwd_drop_hd128_bf16, ext.ob_flash_bwd_d_drop_hd128_bf16)
+    if hd == 128 else
+    (ext.ob_flash_fwd_nt_drop_bf16, ext.ob_flash_bwd_nt_d_drop_bf16))
+
+
 def fwd_drop():
-    check(ext.ob_flash_fwd_nt_drop_bf16(
+    check(fwd_drop_entry(
         ptr(qkv), ptr(O), ptr(lse), B, S, H, nh, scale, DROP_KEY[0],
         DROP_KEY[1], DROP_KEY[2], args.attn_pdrop, stream()))
 
 
 def bwd_drop(bias=None):
-    check(ext.ob_flash_bwd_nt_d_drop_bf16(
+    check(bwd_drop_entry(
         ptr(qkv), ptr(O), ptr(dO), ptr(lse), ptr(D_ws), ptr(dqkv), ptr(bias),
         B, S, H, nh, scale, DROP_KEY[0], DROP_KEY[1], DROP_KEY[2],
         args.attn_pdrop, stream()))
@@ -162,10 +171,22 @@ if hd == 128:
             ("bwd  nt + bias in-kernel     ", lambda: bwd_new(dbias), 5),
             ("dsum alone                   ", dsum, 0),
             ("bwd  nt, D in-kernel, + bias ", lambda: bwd_new_d(dbias), 5)]
+    took = {}
     for name, fn, gemms in rows:
-        us = timeit(fn) * 1e3
+        us = took[name] = timeit(fn) * 1e3
         tf = f" {gemms * unit / (us * 1e-6):7.1f} TF" if gemms else ""
         print(f"{name} {us:8.1f} us{tf}")
+    if args.attn_pdrop > 0.0:
+        fwd_drop()  # the dropout backward reads this forward's O and lse
+        torch.cuda.synchronize()
+        for name, fn, gemms, plain in (
+                (f"fwd  dropout p={args.attn_pdrop}           ", fwd_drop, 2,
+                 rows[0][0]),
+                (f"bwd  dropout p={args.attn_pdrop}, D, + bias", lambda:
+                 bwd_drop(dbias), 5, rows[4][0])):
+            us = timeit(fn) * 1e3
+            print(f"{name} {us:8.1f} us {gemms * unit / (us * 1e-6):7.1f} TF"
+                  f"  x{us / took[plain]:.2f} of the plain row")
     sys.exit(0)
 
 O_old = torch.empty_like(O)
