@@ -67,6 +67,12 @@ typedef struct {
                            deepspeed-compatible num_pipe_buffers) */
   int32_t dtype;        /* 0 = fp32; 1 = bf16 activations/GEMMs with fp32
                            master weights + fp32 grads (§8 f4) */
+  int32_t attn_window;  /* BLOCK: 0 = dense causal attention.  W > 0: locally
+                           banded, query i sees keys i-W < j <= i
+                           (ob_flash_*_win_bf16); W >= seq_len is dense.  A
+                           banded layer must be flash-eligible with
+                           attn_pdrop == 0, else the create fails.  A
+                           zero-filled or keyword-built description is dense */
 } ob_layer_desc;
 
 /* Number of fp32 elements in the layer's flat parameter buffer.  Layout is
@@ -483,6 +489,20 @@ int ob_flash_bwd_d_drop_hd128_bf16(const void* qkv, const void* O,
                                    int64_t nh, float scale, uint64_t seed,
                                    int32_t layer_id, uint64_t tick, float p,
                                    void* stream);
+/* Locally banded (sliding-window) causal flash attention: query row i attends
+ * the keys j with i - window < j <= i.  Kernels of their own
+ * (ob_flash_win_bf16.hip) whose work grows with Sq * window; the shape rules,
+ * buffers, LSE, D_ws and dbias_qkv contracts of ob_flash_fwd_nt_bf16 /
+ * ob_flash_bwd_nt_d_bf16.  window is any integer >= 0; 0 or >= Sq calls the
+ * dense entry (bit-identical to it).  No dropout variant. */
+int ob_flash_fwd_win_bf16(const void* qkv, void* O, void* lse, int64_t B,
+                          int64_t Sq, int64_t H, int64_t nh, int64_t window,
+                          float scale, void* stream);
+int ob_flash_bwd_win_d_bf16(const void* qkv, const void* O, const void* dO,
+                            const void* lse, void* D_ws, void* dqkv,
+                            void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
+                            int64_t nh, int64_t window, float scale,
+                            void* stream);
 /* Host-only queries of the block -> work mapping of the three kernels above
  * (no GPU call).  kind: 0 forward, 1 dq, 2 dkdv.
  * rows: unit = wave 0..3 (forward, dq) or wave pair 0..1 (dkdv) of `block`

@@ -24,6 +24,7 @@ class ObLayerDesc(ctypes.Structure):
         ("seq_len", ctypes.c_int32),
         ("n_slots", ctypes.c_int32),
         ("dtype", ctypes.c_int32),
+        ("attn_window", ctypes.c_int32),  # 0 = dense (the default)
     ]
 
 
@@ -184,6 +185,11 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
                                          i64, i64, f32, vp]
     lib.ob_flash_bwd_nt_d_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64,
                                            i64, i64, i64, f32, vp]
+    # locally banded: `window` follows nh
+    lib.ob_flash_fwd_win_bf16.argtypes = [vp, vp, vp, i64, i64, i64, i64,
+                                          i64, f32, vp]
+    lib.ob_flash_bwd_win_d_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64,
+                                            i64, i64, i64, i64, f32, vp]
     # (seed, layer_id, tick, p): the site is always DROP_ATTN
     lib.ob_flash_fwd_nt_drop_bf16.argtypes = [vp, vp, vp, i64, i64, i64, i64,
                                               f32, u64, i32, u64, f32, vp]

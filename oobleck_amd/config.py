@@ -21,6 +21,13 @@ class ModelConfig:
     embd_pdrop: float = 0.0
     resid_pdrop: float = 0.0
     attn_pdrop: float = 0.0
+    # Locally banded attention (GPT-3's and GPT-Neo's "local" layers): a
+    # banded block's query i sees the keys i - attn_window < j <= i.  0 = every
+    # block dense.  Block b is banded when b % attn_window_every ==
+    # attn_window_every - 1: every=2 alternates dense, banded, ... (GPT-Neo's
+    # order), every=1 bands every block.
+    attn_window: int = 0
+    attn_window_every: int = 2
 
     @property
     def n_layers_total(self) -> int:
@@ -35,6 +42,15 @@ class ModelConfig:
         if layer_id == self.n_layers_total - 1:
             return KIND_FINAL
         return KIND_BLOCK
+
+    def layer_attn_window(self, layer_id: int) -> int:
+        """The attention window of layer `layer_id` (0 = dense; EMBED and
+        FINAL layers always 0)."""
+        from .params import KIND_BLOCK
+        if self.attn_window <= 0 or self.layer_kind(layer_id) != KIND_BLOCK:
+            return 0
+        every = self.attn_window_every
+        return self.attn_window if (layer_id - 1) % every == every - 1 else 0
 
 
 GPT2_SMALL = ModelConfig()

@@ -102,30 +102,8 @@ static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); 
 // The transposed read needs EXEC all ones and 8-byte-aligned lane
 // addresses: every call below sits under wave-uniform control only.
 // ===========================================================================
-__device__ __forceinline__ int nt_key(int row) {
-  return (((row >> 1) & 1) << 2) | ((row >> 2) & 3);
-}
-// element offset of 16-byte chunk `ch` (0..7) of row `row`
-__device__ __forceinline__ int nt_off(int row, int ch) {
-  return row * 64 + ((ch ^ nt_key(row)) << 3);
-}
-// B fragment (32x32x16, k-slab rows r0..r0+7, r0 % 8 == 0) of column
-// 32*dhalf + (lane&31) from the row-major tile: two transposed reads of
-// the 4x16 blocks at rows r0 / r0+4, first column 32*dhalf + 16*(il>>4).
-// Lane i = lane&15 supplies row (i>>2), columns 4*(i&3)..+3 of its block.
-__device__ __forceinline__ bf16x8 nt_tr_frag(const __bf16* tile, int lane,
-                                             int r0, int dhalf) {
-  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-  const int i = lane & 15;
-  const int row = r0 + (i >> 2);
-  const int ch = 4 * dhalf + 2 * ((lane >> 4) & 1) + ((i >> 1) & 1);
-  const int sub = 4 * (i & 1);
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (lds_bf16x4*)(tile + nt_off(row, ch) + sub));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (lds_bf16x4*)(tile + nt_off(row + 4, ch) + sub));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
+// nt_key / nt_off / nt_tr_frag are in ob_flash_common.h (the banded kernels
+// of ob_flash_win_bf16.hip use the same image).
 
 // Attention dropout (kDrop instantiations): the mask
 // definition and drop_crow / drop_bits_q / drop_factor_bit are in

@@ -1,5 +1,6 @@
 // ob_flash_common.h — what the flash kernel files share (ob_flash_bf16.hip:
-// head_dim 64; ob_flash_hd128_bf16.hip: head_dim 128): the MFMA fragment
+// head_dim 64; ob_flash_hd128_bf16.hip: head_dim 128; ob_flash_win_bf16.hip:
+// the locally banded kernels of both sizes): the MFMA fragment
 // types, the P -> A-fragment pack-and-exchange, the accumulator row map, and
 // the in-register attention dropout mask helpers, and the C++ launchers of
 // the hd-128 kernels that the public entries in ob_flash_bf16.hip dispatch
@@ -49,6 +50,60 @@ __device__ __forceinline__ bf16x8 bf_dance(const float* pv8) {
 // tile row of accumulator element r in lane half kh (the C/D layout above)
 __device__ __forceinline__ int acc_row(int r, int kh) {
   return (r & 3) + 8 * (r >> 2) + 4 * kh;
+}
+
+// LDS images of a row-major bf16 tile and the transposed (column-wise) B
+// fragment read from it.  nt_*: [rows][64], 128-byte rows, derived in
+// ob_flash_bf16.hip; hd_*: [rows][128], 256-byte rows, derived in
+// ob_flash_hd128_bf16.hip.  The transposed read needs EXEC all ones.
+__device__ __forceinline__ int nt_key(int row) {
+  return (((row >> 1) & 1) << 2) | ((row >> 2) & 3);
+}
+// element offset of 16-byte chunk `ch` (0..7) of row `row`
+__device__ __forceinline__ int nt_off(int row, int ch) {
+  return row * 64 + ((ch ^ nt_key(row)) << 3);
+}
+// B fragment (32x32x16, k-slab rows r0..r0+7, r0 % 8 == 0) of column
+// 32*dhalf + (lane&31) from the row-major tile: two transposed reads of
+// the 4x16 blocks at rows r0 / r0+4, first column 32*dhalf + 16*(il>>4).
+// Lane i = lane&15 supplies row (i>>2), columns 4*(i&3)..+3 of its block.
+__device__ __forceinline__ bf16x8 nt_tr_frag(const __bf16* tile, int lane,
+                                             int r0, int dhalf) {
+  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+  const int i = lane & 15;
+  const int row = r0 + (i >> 2);
+  const int ch = 4 * dhalf + 2 * ((lane >> 4) & 1) + ((i >> 1) & 1);
+  const int sub = 4 * (i & 1);
+  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+      (lds_bf16x4*)(tile + nt_off(row, ch) + sub));
+  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+      (lds_bf16x4*)(tile + nt_off(row + 4, ch) + sub));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+__device__ __forceinline__ int hd_key(int row) {
+  return ((row & 3) << 2) | ((row >> 2) & 3);
+}
+// element offset of 16-byte chunk `ch` (0..15) of row `row`
+__device__ __forceinline__ int hd_off(int row, int ch) {
+  return row * 128 + ((ch ^ hd_key(row)) << 3);
+}
+// B fragment (32x32x16, k-slab rows r0..r0+7, r0 % 8 == 0) of column
+// 32*dq + (lane&31) from the row-major tile: two transposed reads of the
+// 4x16 blocks at rows r0 / r0+4, first column 32*dq + 16*(il>>4).  Lane
+// i = lane&15 supplies row (i>>2), columns 4*(i&3)..+3 of its block.
+__device__ __forceinline__ bf16x8 hd_tr_frag(const __bf16* tile, int lane,
+                                             int r0, int dq) {
+  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+  const int i = lane & 15;
+  const int row = r0 + (i >> 2);
+  const int ch = 4 * dq + 2 * ((lane >> 4) & 1) + ((i >> 1) & 1);
+  const int sub = 4 * (i & 1);
+  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+      (lds_bf16x4*)(tile + hd_off(row, ch) + sub));
+  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+      (lds_bf16x4*)(tile + hd_off(row + 4, ch) + sub));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 // Attention dropout.  The mask

@@ -72,30 +72,8 @@ static inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); 
 // with __launch_bounds__(256, 1) on that kernel, and re-take the table.
 #define OB_DROP_KERNEL __attribute__((target("no-packed-fp32-ops")))
 
-__device__ __forceinline__ int hd_key(int row) {
-  return ((row & 3) << 2) | ((row >> 2) & 3);
-}
-// element offset of 16-byte chunk `ch` (0..15) of row `row`
-__device__ __forceinline__ int hd_off(int row, int ch) {
-  return row * 128 + ((ch ^ hd_key(row)) << 3);
-}
-// B fragment (32x32x16, k-slab rows r0..r0+7, r0 % 8 == 0) of column
-// 32*dq + (lane&31) from the row-major tile: two transposed reads of the
-// 4x16 blocks at rows r0 / r0+4, first column 32*dq + 16*(il>>4).  Lane
-// i = lane&15 supplies row (i>>2), columns 4*(i&3)..+3 of its block.
-__device__ __forceinline__ bf16x8 hd_tr_frag(const __bf16* tile, int lane,
-                                             int r0, int dq) {
-  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-  const int i = lane & 15;
-  const int row = r0 + (i >> 2);
-  const int ch = 4 * dq + 2 * ((lane >> 4) & 1) + ((i >> 1) & 1);
-  const int sub = 4 * (i & 1);
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (lds_bf16x4*)(tile + hd_off(row, ch) + sub));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-      (lds_bf16x4*)(tile + hd_off(row + 4, ch) + sub));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
+// hd_key / hd_off / hd_tr_frag are in ob_flash_common.h (the banded kernels
+// of ob_flash_win_bf16.hip use the same image).
 
 // Forward: k_flash_fwd_nt's structure (4 waves x 32 q rows, the two folded
 // 64-row halves, KVBLK 64, K/V double-buffered in LDS, one barrier per

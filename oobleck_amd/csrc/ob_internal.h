@@ -208,6 +208,15 @@ int ob_flash_bwd_nt_d_bf16(const void* qkv, const void* O, const void* dO,
                            const void* lse, void* D_ws, void* dqkv,
                            void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
                            int64_t nh, float scale, void* stream);
+// locally banded variants (ob_flash_win_bf16.hip)
+int ob_flash_fwd_win_bf16(const void* qkv, void* O, void* lse, int64_t B,
+                          int64_t Sq, int64_t H, int64_t nh, int64_t window,
+                          float scale, void* stream);
+int ob_flash_bwd_win_d_bf16(const void* qkv, const void* O, const void* dO,
+                            const void* lse, void* D_ws, void* dqkv,
+                            void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
+                            int64_t nh, int64_t window, float scale,
+                            void* stream);
 }
 // The reductions' common form (ob_kernels_bf16.hip): ws null runs the
 // atomic kernels, as the entries above do; ws non-null (deterministic mode)

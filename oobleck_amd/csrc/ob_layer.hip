@@ -881,6 +881,13 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
                            1.f / sqrtf((float)hd), l->seed, l->layer_id,
                            l->slot_tick[slot], l->p_attn, stream)))
         return 1;
+    } else if (ob_plan_windowed(l->d)) {
+      // locally banded layer (the plan admits it with attn_pdrop == 0 only)
+      if (OB_PROF(OB_PF_FLASH_FWD, stream,
+                  ob_flash_fwd_win_bf16(s.qkv, s.am, s.lseP, B, Sq, H, nh,
+                                        l->d.attn_window,
+                                        1.f / sqrtf((float)hd), stream)))
+        return 1;
     } else if (OB_PROF(OB_PF_FLASH_FWD, stream,
                        ob_flash_fwd_nt_bf16(s.qkv, s.am, s.lseP, B, Sq, H, nh,
                                             1.f / sqrtf((float)hd), stream)))
@@ -1099,6 +1106,12 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
                   bwd_drop(s.qkv, s.am, w.DATT, s.lseP, w.D, w.DQKV, dbq, B,
                            Sq, H, nh, scale, l->seed, l->layer_id,
                            l->slot_tick[slot], l->p_attn, stream)))
+        return 1;
+    } else if (ob_plan_windowed(l->d)) {
+      if (OB_PROF(OB_PF_FLASH_BWD, stream,
+                  ob_flash_bwd_win_d_bf16(s.qkv, s.am, w.DATT, s.lseP, w.D,
+                                          w.DQKV, dbq, B, Sq, H, nh,
+                                          l->d.attn_window, scale, stream)))
         return 1;
     } else if (OB_PROF(OB_PF_FLASH_BWD, stream,
                        ob_flash_bwd_nt_d_bf16(s.qkv, s.am, w.DATT, s.lseP, w.D,

@@ -86,8 +86,16 @@ inline int64_t ob_v_pad(int64_t V) { return (V + 255) / 256 * 256; }
 // 0.  head_dim 128 has production kernels only (no OB_FLASH_TR=0 twins);
 // only the production kernels have dropout variants, and the head_dim 128
 // ones are taken only with flash_hd128_drop on.
+// A banded layer (ob_plan_windowed) is a flash layer under the same
+// conditions plus attn_pdrop == 0 and flash_tr: the banded kernels
+// (ob_flash_win_bf16.hip) are production-only and have no dropout variants.
+inline bool ob_plan_windowed(const ob_layer_desc& d) {
+  return d.kind == OB_KIND_BLOCK && d.attn_window > 0 &&
+         d.attn_window < d.seq_len;
+}
 inline bool ob_plan_flash(const ob_layer_desc& d, float p_attn,
                           const ob_layer_modes& m) {
+  if (ob_plan_windowed(d) && (p_attn > 0.f || !m.flash_tr)) return false;
   if (p_attn > 0.f && !(m.flash_tr && m.flash_drop)) return false;
   if (!m.bf16_flash || d.kind != OB_KIND_BLOCK || d.dtype != 1 ||
       d.n_head <= 0 || d.n_embd % d.n_head || d.seq_len <= 0 ||
@@ -122,6 +130,14 @@ inline ob_layer_plan ob_layer_plan_of(const ob_layer_desc& d, float p_resid,
       p.ids_count = BS * d.n_slots;
       break;
     case OB_KIND_BLOCK:
+      // the materialized-P route has no band
+      if (d.attn_window < 0)
+        p.error = "attn_window must be >= 0";
+      else if (ob_plan_windowed(d) && !p.flash)
+        p.error =
+            "0 < attn_window < seq_len needs a flash layer: bf16, head_dim "
+            "64 or 128, seq_len % 128 == 0, attn_pdrop == 0, and none of "
+            "OB_BF16_FLASH=0, OB_FLASH_TR=0, OB_FLASH_HD128=0 (head_dim 128)";
       st(ST_X, BSH), st(ST_MEAN1, BS), st(ST_RSTD1, BS), st(ST_LN1, BSH);
       st(ST_QKV, 3 * BSH), st(ST_P, p.flash ? Bm * nh * Sq : PSS);
       st(ST_ATTNM, BSH), st(ST_HMID, BSH), st(ST_MEAN2, BS), st(ST_RSTD2, BS);

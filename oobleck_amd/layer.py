@@ -50,11 +50,15 @@ class Layer:
                  init_style: str = "gpt2", seed: int = 42,
                  dtype: str = "f32", embd_pdrop: float | None = None,
                  resid_pdrop: float | None = None,
-                 attn_pdrop: float | None = None, dropout_seed: int = 0):
+                 attn_pdrop: float | None = None, dropout_seed: int = 0,
+                 attn_window: int | None = None):
         """Dropout: the three probabilities default to the ModelConfig's;
         with all of them 0 the layer is created by ob_layer_create and is
         exactly the dropout-free layer.  Masks are stateless functions of
-        (dropout_seed, layer_id, site, tick, element) — see forward_slot."""
+        (dropout_seed, layer_id, site, tick, element) — see forward_slot.
+        attn_window: None takes cfg.layer_attn_window(layer_id); W > 0 makes
+        a BLOCK's attention locally banded (flash-eligible bf16 layers with
+        attn_pdrop == 0 only: anything else fails in the create)."""
         self.layer_id = layer_id
         self.cfg = cfg
         self.kind = cfg.layer_kind(layer_id)
@@ -62,12 +66,15 @@ class Layer:
         assert dtype in ("f32", "bf16")
         self.dtype = dtype
         self.act_dtype = torch.float32 if dtype == "f32" else torch.bfloat16
+        if attn_window is None:
+            attn_window = cfg.layer_attn_window(layer_id)
+        self.attn_window = int(attn_window)
         ext = get_ext()
         self._desc = ObLayerDesc(
             kind=self.kind, n_embd=cfg.n_embd, n_head=cfg.n_head,
             n_positions=cfg.n_positions, vocab_size=cfg.vocab_size,
             max_batch=max_batch, seq_len=seq_len, n_slots=n_slots,
-            dtype=0 if dtype == "f32" else 1)
+            dtype=0 if dtype == "f32" else 1, attn_window=self.attn_window)
         n = ext.ob_layer_param_count(ctypes.byref(self._desc))
         assert n > 0
         init = init_layer_params(cfg, layer_id, seed, init_style).to(device)

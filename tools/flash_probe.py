@@ -17,6 +17,16 @@
 # entries (ob_flash_fwd_drop_hd128_bf16 / ob_flash_bwd_d_drop_hd128_bf16)
 # and their ratio to the plain rows.  The default, --head-dim 64, prints what
 # it always did.
+#
+# --window W (0 < W < S) times the locally banded entries
+# (ob_flash_fwd_win_bf16 / ob_flash_bwd_win_d_bf16) against the dense ones at
+# --head-dim / --shape: the two arms alternate, --repeats times, each repeat
+# the mean of 30 back-to-back calls between device events; it prints every
+# repeat, min / max per arm and dense / window of the minima, with the dense
+# arm's own max - min next to the margin.  The backward rows are dq + dkdv
+# together; the three kernels on their own come from a kernel trace of this
+# same command (tools/kstats.py), where the two arms' kernels have different
+# names.
 import argparse
 import ctypes
 import pathlib
@@ -32,6 +42,9 @@ ap.add_argument("--attn-pdrop", type=float, default=0.0, metavar="P",
                 help="also time the dropout variants of the three kernels")
 ap.add_argument("--head-dim", type=int, default=64, choices=(64, 128))
 ap.add_argument("--shape", default="8,12,1024", metavar="B,nh,S")
+ap.add_argument("--window", type=int, default=0, metavar="W",
+                help="time the banded entries against the dense ones")
+ap.add_argument("--repeats", type=int, default=7)
 args = ap.parse_args()
 
 B, nh, S = (int(v) for v in args.shape.split(","))
@@ -159,6 +172,57 @@ def bwd_drop(bias=None):
         B, S, H, nh, scale, DROP_KEY[0], DROP_KEY[1], DROP_KEY[2],
         args.attn_pdrop, stream()))
 
+
+def timeit_once(fn, reps=30):
+    st, en = torch.cuda.Event(True), torch.cuda.Event(True)
+    st.record()
+    for _ in range(reps):
+        fn()
+    en.record()
+    torch.cuda.synchronize()
+    return st.elapsed_time(en) / reps * 1e3
+
+
+if args.window:
+    W = args.window
+    assert 0 < W < S, "--window must be in (0, S)"
+
+    def fwd_win():
+        check(ext.ob_flash_fwd_win_bf16(ptr(qkv), ptr(O), ptr(lse), B, S, H,
+                                        nh, W, scale, stream()))
+
+    def bwd_win():
+        check(ext.ob_flash_bwd_win_d_bf16(
+            ptr(qkv), ptr(O), ptr(dO), ptr(lse), ptr(D_ws), ptr(dqkv),
+            ptr(dbias), B, S, H, nh, W, scale, stream()))
+
+    work = (S * W - W * W / 2) / (S * S / 2)
+    print(f"head_dim {hd}, (B, nh, S) = ({B}, {nh}, {S}), window {W}: "
+          f"band / triangle = {work:.3f} of the MFMA work")
+    # each backward reads the O and lse of its own arm's forward
+    for name, dense, win, pre in (
+            ("fwd", fwd_new, fwd_win, (None, None)),
+            ("bwd (dq + dkdv, D in-kernel, + bias)",
+             lambda: bwd_new_d(dbias), bwd_win, (fwd_new, fwd_win))):
+        for fn in (dense, win):
+            for _ in range(5):
+                fn()
+        torch.cuda.synchronize()
+        us = ([], [])
+        for _ in range(args.repeats):
+            for arm, fn in enumerate((dense, win)):
+                if pre[arm]:
+                    pre[arm]()
+                us[arm].append(timeit_once(fn))
+        d, w_ = us
+        print(f"{name}")
+        print("  dense  us: " + " ".join(f"{v:7.1f}" for v in d))
+        print("  window us: " + " ".join(f"{v:7.1f}" for v in w_))
+        print(f"  dense min {min(d):.1f} max {max(d):.1f} (spread "
+              f"{max(d) - min(d):.1f}); window min {min(w_):.1f} max "
+              f"{max(w_):.1f}; dense / window = {min(d) / min(w_):.2f}; "
+              f"margin {min(d) - max(w_):.1f} us")
+    sys.exit(0)
 
 if hd == 128:
     fwd_new()
