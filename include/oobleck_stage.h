@@ -69,7 +69,8 @@ typedef struct {
                            master weights + fp32 grads (§8 f4) */
   int32_t attn_window;  /* BLOCK: 0 = dense causal attention.  W > 0: locally
                            banded, query i sees keys i-W < j <= i
-                           (ob_flash_*_win_bf16); W >= seq_len is dense.  A
+                           (ob_flash_*_win_bf16; head_dim 80 / 96:
+                           ob_flash_*_hd96_*bf16); W >= seq_len is dense.  A
                            banded layer must be flash-eligible with
                            attn_pdrop == 0, else the create fails.  A
                            zero-filled or keyword-built description is dense */
@@ -121,7 +122,8 @@ int ob_layer_create_ex(const ob_layer_desc* desc, const ob_dropout_desc* drop,
  * 64, for attn_pdrop > 0, neither OB_FLASH_DROP=0 nor OB_FLASH_TR=0; at
  * head_dim 128 neither OB_FLASH_TR=0 nor OB_FLASH_HD128=0 and, for
  * attn_pdrop > 0, also OB_FLASH_HD128_DROP=1 (default 0) and not
- * OB_FLASH_DROP=0), 0 otherwise.  Host-only. */
+ * OB_FLASH_DROP=0; head_dim 80 or 96 only with OB_FLASH_HD96=1 (default 0),
+ * attn_pdrop == 0 and not OB_FLASH_TR=0), 0 otherwise.  Host-only. */
 int ob_layer_uses_flash(ob_layer_t l);
 /* The same decision for a description, before any layer exists: what
  * ob_layer_create_ex will take for `desc` with this attn_pdrop.  Host-only,
@@ -131,8 +133,8 @@ int ob_flash_eligible(const ob_layer_desc* desc, float attn_pdrop);
 /* The device memory ob_layer_create_ex takes for `desc` (drop may be null),
  * from the same table the create allocates by (DESIGN.md "Layer memory").
  * modes: bit 0 deterministic, 1 OB_BF16_FLASH, 2 OB_FLASH_TR, 3
- * OB_FLASH_DROP, 4 OB_FLASH_HD128, 5 OB_FLASH_HD128_DROP (a set bit = that
- * switch on); -1 = this process's.  Writes up to cap int64s and returns the
+ * OB_FLASH_DROP, 4 OB_FLASH_HD128, 5 OB_FLASH_HD128_DROP, 6 OB_FLASH_HD96 (a
+ * set bit = that switch on); -1 = this process's.  Writes up to cap int64s and returns the
  * field count (-1 on a null argument).  Fields, in order: flash, side (needs the side stream),
  * v_pad, slot_stride (floats of one stash slot), ids_count (int64s, all
  * slots), shadow_count (bf16 elements); the 15 stash regions' offsets within
@@ -503,6 +505,21 @@ int ob_flash_bwd_win_d_bf16(const void* qkv, const void* O, const void* dO,
                             void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
                             int64_t nh, int64_t window, float scale,
                             void* stream);
+/* head_dim 80 and 96 (H == 80 * nh or 96 * nh; GPT-3 2.7B and 760M), dense
+ * and locally banded in one kernel set (ob_flash_hd96_bf16.hip).  Argument
+ * order and contracts of ob_flash_fwd_win_bf16 / ob_flash_bwd_win_d_bf16:
+ * Sq % 128 == 0, window >= 0 where 0 and >= Sq are the same dense launch; the
+ * dq kernel writes D_ws for the dkdv launch; a null dbias_qkv skips the bias
+ * sum.  Any other shape returns 1 with the error set and launches nothing;
+ * the entries above keep refusing these head sizes.  No dropout variant. */
+int ob_flash_fwd_hd96_bf16(const void* qkv, void* O, void* lse, int64_t B,
+                           int64_t Sq, int64_t H, int64_t nh, int64_t window,
+                           float scale, void* stream);
+int ob_flash_bwd_hd96_d_bf16(const void* qkv, const void* O, const void* dO,
+                             const void* lse, void* D_ws, void* dqkv,
+                             void* dbias_qkv, int64_t B, int64_t Sq,
+                             int64_t H, int64_t nh, int64_t window,
+                             float scale, void* stream);
 /* Host-only queries of the block -> work mapping of the three kernels above
  * (no GPU call).  kind: 0 forward, 1 dq, 2 dkdv.
  * rows: unit = wave 0..3 (forward, dq) or wave pair 0..1 (dkdv) of `block`

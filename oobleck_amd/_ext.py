@@ -190,6 +190,11 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
                                           i64, f32, vp]
     lib.ob_flash_bwd_win_d_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64,
                                             i64, i64, i64, i64, f32, vp]
+    # head_dim 80 / 96, dense and banded: the banded argument lists
+    lib.ob_flash_fwd_hd96_bf16.argtypes = (
+        lib.ob_flash_fwd_win_bf16.argtypes)
+    lib.ob_flash_bwd_hd96_d_bf16.argtypes = (
+        lib.ob_flash_bwd_win_d_bf16.argtypes)
     # (seed, layer_id, tick, p): the site is always DROP_ATTN
     lib.ob_flash_fwd_nt_drop_bf16.argtypes = [vp, vp, vp, i64, i64, i64, i64,
                                               f32, u64, i32, u64, f32, vp]
@@ -344,6 +349,7 @@ LAYER_PLAN_NAMES = (
 PLAN_DET, PLAN_BF16_FLASH, PLAN_FLASH_TR, PLAN_FLASH_DROP, PLAN_FLASH_HD128 = (
     1, 2, 4, 8, 16)
 PLAN_FLASH_HD128_DROP = 32  # OB_FLASH_HD128_DROP, off by default
+PLAN_FLASH_HD96 = 64  # OB_FLASH_HD96, off by default
 
 
 def layer_plan(desc: ObLayerDesc, drop: ObDropoutDesc | None = None,

@@ -60,6 +60,9 @@ GPT2_XL = ModelConfig(n_embd=1600, n_head=25, n_layer=48, n_positions=1024)
 # GPT-3 sizes (Brown et al. 2020, table 2.1); both have head_dim 128
 GPT3_1_3B = ModelConfig(n_embd=2048, n_head=16, n_layer=24, n_positions=2048)
 GPT3_6_7B = ModelConfig(n_embd=4096, n_head=32, n_layer=32, n_positions=2048)
+# head_dim 96 and 80: flash layers only with OB_FLASH_HD96=1
+GPT3_760M = ModelConfig(n_embd=1536, n_head=16, n_layer=24, n_positions=2048)
+GPT3_2_7B = ModelConfig(n_embd=2560, n_head=32, n_layer=32, n_positions=2048)
 
 
 @dataclass

@@ -1,6 +1,7 @@
 // ob_flash_common.h — what the flash kernel files share (ob_flash_bf16.hip:
 // head_dim 64; ob_flash_hd128_bf16.hip: head_dim 128; ob_flash_win_bf16.hip:
-// the locally banded kernels of both sizes): the MFMA fragment
+// the locally banded kernels of both sizes; ob_flash_hd96_bf16.hip: head_dim
+// 80 and 96, dense and banded): the MFMA fragment
 // types, the P -> A-fragment pack-and-exchange, the accumulator row map, and
 // the in-register attention dropout mask helpers, and the C++ launchers of
 // the hd-128 kernels that the public entries in ob_flash_bf16.hip dispatch
@@ -103,6 +104,48 @@ __device__ __forceinline__ bf16x8 hd_tr_frag(const __bf16* tile, int lane,
       (lds_bf16x4*)(tile + hd_off(row, ch) + sub));
   const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
       (lds_bf16x4*)(tile + hd_off(row + 4, ch) + sub));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// h96_*: [rows][96], 192-byte rows of twelve 16-byte chunks: the image of the
+// head_dim 80 and 96 kernels (ob_flash_hd96_bf16.hip; at 80 chunks 10 and 11
+// are padding).  Twelve is no power of two, so an XOR key over the whole chunk
+// index (nt_key, hd_key) would leave the row; the key here flips the low two
+// chunk bits only and stays inside an aligned group of 4 chunks:
+//   chunk ch of row r lives at chunk slot  ch ^ key(r),  key(r) = (r>>2)&3.
+// Bank = (byte/4) % 64: a 256-byte sweep holds sixteen 16-byte slots, and row
+// r starts at slot 12r % 16 = 4 * ((-r) & 3).  So chunk ch of row r has sweep
+// slot bits 3:2 = ((ch>>2) - r) & 3 and bits 1:0 = (ch&3) ^ ((r>>2)&3): the
+// unpadded pitch rotates the groups of 4 by the row's low bits, the key
+// permutes inside a group by the next two.
+//  * transposed read, one 32-lane half = rows r0..r0+3 (r0 % 4 == 0) x one
+//    aligned group of 4 chunks: bits 3:2 take one value per row, bits 1:0 are
+//    a permutation inside the group -> 16 distinct slots, conflict-free.
+//  * ds_read_b128 row read (lane il -> row il, one chunk index per half): its
+//    16-lane groups hold rows {0-3,12-15,20-27} / {4-11,16-19,28-31}, four
+//    aligned runs of 4 rows whose (r>>2)&3 are 0,3,1,2 / 1,2,0,3.  Inside a
+//    run bits 3:2 take all four values; across the runs bits 1:0 do -> 16
+//    distinct slots, conflict-free.
+// key has period 16 in r, as hd_key.
+__device__ __forceinline__ int h96_key(int row) { return (row >> 2) & 3; }
+// element offset of 16-byte chunk `ch` (0..11) of row `row`
+__device__ __forceinline__ int h96_off(int row, int ch) {
+  return row * 96 + ((ch ^ h96_key(row)) << 3);
+}
+// B fragment (32x32x16, k-slab rows r0..r0+7, r0 % 8 == 0) of column
+// 32*dt + (lane&31), dt = 0..2, from the row-major tile: the two transposed
+// reads of hd_tr_frag.
+__device__ __forceinline__ bf16x8 h96_tr_frag(const __bf16* tile, int lane,
+                                              int r0, int dt) {
+  typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+  const int i = lane & 15;
+  const int row = r0 + (i >> 2);
+  const int ch = 4 * dt + 2 * ((lane >> 4) & 1) + ((i >> 1) & 1);
+  const int sub = 4 * (i & 1);
+  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+      (lds_bf16x4*)(tile + h96_off(row, ch) + sub));
+  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+      (lds_bf16x4*)(tile + h96_off(row + 4, ch) + sub));
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 

@@ -57,8 +57,8 @@
 // templates under attributed __global__ wrappers for the reason given there.
 // Resources: profiles/flash_win_resources.txt (no scratch).
 //
-// Out of scope: dropout with a window, the materialized-P and fp32 routes,
-// head_dim 80/96.
+// Out of scope: dropout with a window, the materialized-P and fp32 routes.
+// head_dim 80/96, dense and banded: ob_flash_hd96_bf16.hip.
 #include "ob_flash_common.h"
 #include "ob_internal.h"
 #include "ob_flash_fold.h"

@@ -302,18 +302,22 @@ static bool no_blaslt() {
 // (ob_flash_*_nt_drop_bf16, ob_flash_hd128_bf16.hip).
 // OB_FLASH_HD128_DROP=1 (default 0) lets a head_dim 128 layer with
 // attn_pdrop > 0 take the flash kernels' dropout variants
-// (ob_flash_*_drop_hd128_bf16) instead of that path.  All read once.
+// (ob_flash_*_drop_hd128_bf16) instead of that path.  OB_FLASH_HD96=1
+// (default 0) lets a head_dim 80 or 96 layer with attn_pdrop == 0 take the
+// kernels of ob_flash_hd96_bf16.hip, dense or banded.  All read once.
 static ob_layer_modes process_modes() {
   static const bool fl = ob_env_flag("OB_BF16_FLASH", true),
                     drop = ob_env_flag("OB_FLASH_DROP", true),
                     hd128 = ob_env_flag("OB_FLASH_HD128", true),
-                    hd128_drop = ob_env_flag("OB_FLASH_HD128_DROP", false);
-  return {ob_deterministic() != 0, fl, flash_tr(), drop, hd128, hd128_drop};
+                    hd128_drop = ob_env_flag("OB_FLASH_HD128_DROP", false),
+                    hd96 = ob_env_flag("OB_FLASH_HD96", false);
+  return {ob_deterministic() != 0, fl, flash_tr(), drop, hd128, hd128_drop,
+          hd96};
 }
 static ob_layer_modes modes_of_bits(int bits) {
   if (bits < 0) return process_modes();
   return {(bits & 1) != 0, (bits & 2) != 0, (bits & 4) != 0, (bits & 8) != 0,
-          (bits & 16) != 0, (bits & 32) != 0};
+          (bits & 16) != 0, (bits & 32) != 0, (bits & 64) != 0};
 }
 
 // the decision ob_layer_create_ex takes for `d` with this attn_pdrop; host
@@ -881,6 +885,13 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
                            1.f / sqrtf((float)hd), l->seed, l->layer_id,
                            l->slot_tick[slot], l->p_attn, stream)))
         return 1;
+    } else if (hd == 80 || hd == 96) {
+      // dense or banded (the plan admits these with attn_pdrop == 0 only)
+      if (OB_PROF(OB_PF_FLASH_FWD, stream,
+                  ob_flash_fwd_hd96_bf16(s.qkv, s.am, s.lseP, B, Sq, H, nh,
+                                         l->d.attn_window,
+                                         1.f / sqrtf((float)hd), stream)))
+        return 1;
     } else if (ob_plan_windowed(l->d)) {
       // locally banded layer (the plan admits it with attn_pdrop == 0 only)
       if (OB_PROF(OB_PF_FLASH_FWD, stream,
@@ -1106,6 +1117,12 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
                   bwd_drop(s.qkv, s.am, w.DATT, s.lseP, w.D, w.DQKV, dbq, B,
                            Sq, H, nh, scale, l->seed, l->layer_id,
                            l->slot_tick[slot], l->p_attn, stream)))
+        return 1;
+    } else if (hd == 80 || hd == 96) {
+      if (OB_PROF(OB_PF_FLASH_BWD, stream,
+                  ob_flash_bwd_hd96_d_bf16(s.qkv, s.am, w.DATT, s.lseP, w.D,
+                                           w.DQKV, dbq, B, Sq, H, nh,
+                                           l->d.attn_window, scale, stream)))
         return 1;
     } else if (ob_plan_windowed(l->d)) {
       if (OB_PROF(OB_PF_FLASH_BWD, stream,

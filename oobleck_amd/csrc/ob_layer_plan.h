@@ -58,6 +58,7 @@ enum {
 struct ob_layer_modes {
   bool det, bf16_flash, flash_tr, flash_drop, flash_hd128;
   bool flash_hd128_drop;  // OB_FLASH_HD128_DROP, off by default
+  bool flash_hd96;        // OB_FLASH_HD96, off by default
 };
 
 struct ob_layer_plan {
@@ -86,9 +87,13 @@ inline int64_t ob_v_pad(int64_t V) { return (V + 255) / 256 * 256; }
 // 0.  head_dim 128 has production kernels only (no OB_FLASH_TR=0 twins);
 // only the production kernels have dropout variants, and the head_dim 128
 // ones are taken only with flash_hd128_drop on.
+// head_dim 80 and 96 (GPT-3 2.7B and 760M; ob_flash_hd96_bf16.hip) are taken
+// only with flash_hd96 on, and with flash_tr and attn_pdrop == 0: those
+// kernels are production-only and have no dropout variants.
 // A banded layer (ob_plan_windowed) is a flash layer under the same
 // conditions plus attn_pdrop == 0 and flash_tr: the banded kernels
-// (ob_flash_win_bf16.hip) are production-only and have no dropout variants.
+// (ob_flash_win_bf16.hip, ob_flash_hd96_bf16.hip) are production-only and
+// have no dropout variants.
 inline bool ob_plan_windowed(const ob_layer_desc& d) {
   return d.kind == OB_KIND_BLOCK && d.attn_window > 0 &&
          d.attn_window < d.seq_len;
@@ -105,6 +110,8 @@ inline bool ob_plan_flash(const ob_layer_desc& d, float p_attn,
   if (hd == 128)
     return m.flash_tr && m.flash_hd128 &&
            (p_attn == 0.f || m.flash_hd128_drop);  // > 0: flash_drop is on
+  if (hd == 80 || hd == 96)
+    return m.flash_hd96 && m.flash_tr && p_attn == 0.f;
   return hd == 64;
 }
 
@@ -136,8 +143,9 @@ inline ob_layer_plan ob_layer_plan_of(const ob_layer_desc& d, float p_resid,
       else if (ob_plan_windowed(d) && !p.flash)
         p.error =
             "0 < attn_window < seq_len needs a flash layer: bf16, head_dim "
-            "64 or 128, seq_len % 128 == 0, attn_pdrop == 0, and none of "
-            "OB_BF16_FLASH=0, OB_FLASH_TR=0, OB_FLASH_HD128=0 (head_dim 128)";
+            "64 or 128 (80 or 96 with OB_FLASH_HD96=1), seq_len % 128 == 0, "
+            "attn_pdrop == 0, and none of OB_BF16_FLASH=0, OB_FLASH_TR=0, "
+            "OB_FLASH_HD128=0 (head_dim 128)";
       st(ST_X, BSH), st(ST_MEAN1, BS), st(ST_RSTD1, BS), st(ST_LN1, BSH);
       st(ST_QKV, 3 * BSH), st(ST_P, p.flash ? Bm * nh * Sq : PSS);
       st(ST_ATTNM, BSH), st(ST_HMID, BSH), st(ST_MEAN2, BS), st(ST_RSTD2, BS);

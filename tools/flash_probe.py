@@ -27,6 +27,12 @@
 # together; the three kernels on their own come from a kernel trace of this
 # same command (tools/kstats.py), where the two arms' kernels have different
 # names.
+#
+# --head-dim 80 / 96 go through ob_flash_fwd_hd96_bf16 /
+# ob_flash_bwd_hd96_d_bf16, whose dense and banded arms are one kernel set:
+# without --window it prints --repeats repeats of the dense forward and
+# backward with min / max and TF; with --window the A/B above (plus the TF of
+# both arms' minima: causal FLOPs times band / triangle for the window arm).
 import argparse
 import ctypes
 import pathlib
@@ -40,7 +46,7 @@ from oobleck_amd._ext import check, get_ext  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--attn-pdrop", type=float, default=0.0, metavar="P",
                 help="also time the dropout variants of the three kernels")
-ap.add_argument("--head-dim", type=int, default=64, choices=(64, 128))
+ap.add_argument("--head-dim", type=int, default=64, choices=(64, 80, 96, 128))
 ap.add_argument("--shape", default="8,12,1024", metavar="B,nh,S")
 ap.add_argument("--window", type=int, default=0, metavar="W",
                 help="time the banded entries against the dense ones")
@@ -150,6 +156,17 @@ def bwd_new_d(bias=None):
         B, S, H, nh, scale, stream()))
 
 
+if hd in (80, 96):  # one entry pair, dense = window 0
+    def fwd_new():
+        check(ext.ob_flash_fwd_hd96_bf16(ptr(qkv), ptr(O), ptr(lse), B, S, H,
+                                         nh, 0, scale, stream()))
+
+    def bwd_new_d(bias=None):
+        check(ext.ob_flash_bwd_hd96_d_bf16(
+            ptr(qkv), ptr(O), ptr(dO), ptr(lse), ptr(D_ws), ptr(dqkv),
+            ptr(bias), B, S, H, nh, 0, scale, stream()))
+
+
 # dropout key: any seed / layer / tick; the cost does not depend on them
 DROP_KEY = ((0xDEADBEEF << 32) | 0x1234567, 5, (1 << 32) + 3)
 
@@ -187,12 +204,17 @@ if args.window:
     W = args.window
     assert 0 < W < S, "--window must be in (0, S)"
 
+    fwd_win_entry, bwd_win_entry = (
+        (ext.ob_flash_fwd_hd96_bf16, ext.ob_flash_bwd_hd96_d_bf16)
+        if hd in (80, 96) else
+        (ext.ob_flash_fwd_win_bf16, ext.ob_flash_bwd_win_d_bf16))
+
     def fwd_win():
-        check(ext.ob_flash_fwd_win_bf16(ptr(qkv), ptr(O), ptr(lse), B, S, H,
+        check(fwd_win_entry(ptr(qkv), ptr(O), ptr(lse), B, S, H,
                                         nh, W, scale, stream()))
 
     def bwd_win():
-        check(ext.ob_flash_bwd_win_d_bf16(
+        check(bwd_win_entry(
             ptr(qkv), ptr(O), ptr(dO), ptr(lse), ptr(D_ws), ptr(dqkv),
             ptr(dbias), B, S, H, nh, W, scale, stream()))
 
@@ -200,10 +222,11 @@ if args.window:
     print(f"head_dim {hd}, (B, nh, S) = ({B}, {nh}, {S}), window {W}: "
           f"band / triangle = {work:.3f} of the MFMA work")
     # each backward reads the O and lse of its own arm's forward
-    for name, dense, win, pre in (
-            ("fwd", fwd_new, fwd_win, (None, None)),
+    unit = B * nh * S * S * hd * 1e-6  # MFLOP per causal GEMM pair / 2
+    for name, dense, win, pre, gemms in (
+            ("fwd", fwd_new, fwd_win, (None, None), 2),
             ("bwd (dq + dkdv, D in-kernel, + bias)",
-             lambda: bwd_new_d(dbias), bwd_win, (fwd_new, fwd_win))):
+             lambda: bwd_new_d(dbias), bwd_win, (fwd_new, fwd_win), 5)):
         for fn in (dense, win):
             for _ in range(5):
                 fn()
@@ -222,6 +245,26 @@ if args.window:
               f"{max(d) - min(d):.1f}); window min {min(w_):.1f} max "
               f"{max(w_):.1f}; dense / window = {min(d) / min(w_):.2f}; "
               f"margin {min(d) - max(w_):.1f} us")
+        print(f"  dense {gemms * unit / min(d):.1f} TF; window "
+              f"{gemms * unit * work / min(w_):.1f} TF")
+    sys.exit(0)
+
+if hd in (80, 96):
+    unit = B * nh * S * S * hd * 1e-6  # MFLOP per causal GEMM pair / 2
+    print(f"head_dim {hd}, (B, nh, S) = ({B}, {nh}, {S})")
+    fwd_new()  # the backward reads this forward's O and lse
+    for name, fn, gemms in (
+            ("fwd", fwd_new, 2),
+            ("bwd (dq + dkdv, D in-kernel, + bias)",
+             lambda: bwd_new_d(dbias), 5)):
+        for _ in range(5):
+            fn()
+        torch.cuda.synchronize()
+        us = [timeit_once(fn) for _ in range(args.repeats)]
+        print(f"{name}")
+        print("  us: " + " ".join(f"{v:7.1f}" for v in us))
+        print(f"  min {min(us):.1f} max {max(us):.1f}; "
+              f"{gemms * unit / min(us):.1f} TF")
     sys.exit(0)
 
 if hd == 128:
