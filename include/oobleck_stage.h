@@ -71,8 +71,9 @@ typedef struct {
                            banded, query i sees keys i-W < j <= i
                            (ob_flash_*_win_bf16; head_dim 80 / 96:
                            ob_flash_*_hd96_*bf16); W >= seq_len is dense.  A
-                           banded layer must be flash-eligible with
-                           attn_pdrop == 0, else the create fails.  A
+                           banded layer must be flash-eligible, with
+                           attn_pdrop == 0 unless OB_FLASH_BAND_DROP=1, else
+                           the create fails.  A
                            zero-filled or keyword-built description is dense */
 } ob_layer_desc;
 
@@ -105,7 +106,10 @@ typedef struct {
                            the masks inside the flash kernels
                            (ob_flash_*_nt_drop_bf16; at head_dim 128
                            ob_flash_*_drop_hd128_bf16, only with
-                           OB_FLASH_HD128_DROP=1); with OB_FLASH_DROP=0 or
+                           OB_FLASH_HD128_DROP=1; banded, or at head_dim
+                           80 / 96, ob_flash_*_win_drop_bf16 and
+                           ob_flash_*_hd96_drop_bf16, only with
+                           OB_FLASH_BAND_DROP=1); with OB_FLASH_DROP=0 or
                            OB_FLASH_TR=0 in the environment, > 0 takes the
                            materialized-P attention path instead */
   int32_t layer_id;     /* 0 <= layer_id < 2^24 */
@@ -123,7 +127,10 @@ int ob_layer_create_ex(const ob_layer_desc* desc, const ob_dropout_desc* drop,
  * head_dim 128 neither OB_FLASH_TR=0 nor OB_FLASH_HD128=0 and, for
  * attn_pdrop > 0, also OB_FLASH_HD128_DROP=1 (default 0) and not
  * OB_FLASH_DROP=0; head_dim 80 or 96 only with OB_FLASH_HD96=1 (default 0),
- * attn_pdrop == 0 and not OB_FLASH_TR=0), 0 otherwise.  Host-only. */
+ * attn_pdrop == 0 and not OB_FLASH_TR=0; with OB_FLASH_BAND_DROP=1 (default
+ * 0) and not OB_FLASH_DROP=0, attn_pdrop > 0 is also taken at head_dim 80 or
+ * 96 and by a banded layer of any of the four head sizes), 0 otherwise.
+ * Host-only. */
 int ob_layer_uses_flash(ob_layer_t l);
 /* The same decision for a description, before any layer exists: what
  * ob_layer_create_ex will take for `desc` with this attn_pdrop.  Host-only,
@@ -133,7 +140,8 @@ int ob_flash_eligible(const ob_layer_desc* desc, float attn_pdrop);
 /* The device memory ob_layer_create_ex takes for `desc` (drop may be null),
  * from the same table the create allocates by (DESIGN.md "Layer memory").
  * modes: bit 0 deterministic, 1 OB_BF16_FLASH, 2 OB_FLASH_TR, 3
- * OB_FLASH_DROP, 4 OB_FLASH_HD128, 5 OB_FLASH_HD128_DROP, 6 OB_FLASH_HD96 (a
+ * OB_FLASH_DROP, 4 OB_FLASH_HD128, 5 OB_FLASH_HD128_DROP, 6 OB_FLASH_HD96, 7
+ * OB_FLASH_BAND_DROP (attn_pdrop > 0 on a banded or head_dim 80 / 96 layer; a
  * set bit = that switch on); -1 = this process's.  Writes up to cap int64s and returns the
  * field count (-1 on a null argument).  Fields, in order: flash, side (needs the side stream),
  * v_pad, slot_stride (floats of one stash slot), ids_count (int64s, all
@@ -496,7 +504,7 @@ int ob_flash_bwd_d_drop_hd128_bf16(const void* qkv, const void* O,
  * (ob_flash_win_bf16.hip) whose work grows with Sq * window; the shape rules,
  * buffers, LSE, D_ws and dbias_qkv contracts of ob_flash_fwd_nt_bf16 /
  * ob_flash_bwd_nt_d_bf16.  window is any integer >= 0; 0 or >= Sq calls the
- * dense entry (bit-identical to it).  No dropout variant. */
+ * dense entry (bit-identical to it).  Dropout: the _drop entries below. */
 int ob_flash_fwd_win_bf16(const void* qkv, void* O, void* lse, int64_t B,
                           int64_t Sq, int64_t H, int64_t nh, int64_t window,
                           float scale, void* stream);
@@ -511,7 +519,8 @@ int ob_flash_bwd_win_d_bf16(const void* qkv, const void* O, const void* dO,
  * Sq % 128 == 0, window >= 0 where 0 and >= Sq are the same dense launch; the
  * dq kernel writes D_ws for the dkdv launch; a null dbias_qkv skips the bias
  * sum.  Any other shape returns 1 with the error set and launches nothing;
- * the entries above keep refusing these head sizes.  No dropout variant. */
+ * the entries above keep refusing these head sizes.  Dropout: the _drop
+ * entries below. */
 int ob_flash_fwd_hd96_bf16(const void* qkv, void* O, void* lse, int64_t B,
                            int64_t Sq, int64_t H, int64_t nh, int64_t window,
                            float scale, void* stream);
@@ -520,6 +529,39 @@ int ob_flash_bwd_hd96_d_bf16(const void* qkv, const void* O, const void* dO,
                              void* dbias_qkv, int64_t B, int64_t Sq,
                              int64_t H, int64_t nh, int64_t window,
                              float scale, void* stream);
+/* The four entries above with attention dropout drawn inside the kernels
+ * (DESIGN.md item 23): the mask, LSE and backward definitions of
+ * ob_flash_fwd_nt_drop_bf16, which depend on neither the head size nor the
+ * window; the backward must be given the forward's key.  The plain entry's
+ * checks, then p in [0,1) and B*nh*Sq*Sq <= 2^34, all before any launch.
+ * p == 0 calls the plain entry.  _win_: window 0 or >= Sq calls the dense
+ * dropout entry of the head size (ob_flash_*_nt_drop_bf16,
+ * ob_flash_*_drop_hd128_bf16), bit-identical to it.  _hd96_: window 0 and
+ * >= Sq are the same dense launch. */
+int ob_flash_fwd_win_drop_bf16(const void* qkv, void* O, void* lse, int64_t B,
+                               int64_t Sq, int64_t H, int64_t nh,
+                               int64_t window, float scale, uint64_t seed,
+                               int32_t layer_id, uint64_t tick, float p,
+                               void* stream);
+int ob_flash_bwd_win_d_drop_bf16(const void* qkv, const void* O,
+                                 const void* dO, const void* lse, void* D_ws,
+                                 void* dqkv, void* dbias_qkv, int64_t B,
+                                 int64_t Sq, int64_t H, int64_t nh,
+                                 int64_t window, float scale, uint64_t seed,
+                                 int32_t layer_id, uint64_t tick, float p,
+                                 void* stream);
+int ob_flash_fwd_hd96_drop_bf16(const void* qkv, void* O, void* lse, int64_t B,
+                                int64_t Sq, int64_t H, int64_t nh,
+                                int64_t window, float scale, uint64_t seed,
+                                int32_t layer_id, uint64_t tick, float p,
+                                void* stream);
+int ob_flash_bwd_hd96_d_drop_bf16(const void* qkv, const void* O,
+                                  const void* dO, const void* lse, void* D_ws,
+                                  void* dqkv, void* dbias_qkv, int64_t B,
+                                  int64_t Sq, int64_t H, int64_t nh,
+                                  int64_t window, float scale, uint64_t seed,
+                                  int32_t layer_id, uint64_t tick, float p,
+                                  void* stream);
 /* Host-only queries of the block -> work mapping of the three kernels above
  * (no GPU call).  kind: 0 forward, 1 dq, 2 dkdv.
  * rows: unit = wave 0..3 (forward, dq) or wave pair 0..1 (dkdv) of `block`

@@ -206,6 +206,17 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
         lib.ob_flash_fwd_nt_drop_bf16.argtypes)
     lib.ob_flash_bwd_d_drop_hd128_bf16.argtypes = (
         lib.ob_flash_bwd_nt_d_drop_bf16.argtypes)
+    # banded and head_dim 80 / 96 with dropout: the banded argument lists
+    # with (seed, layer_id, tick, p) before the stream
+    drop_args = [f32, u64, i32, u64, f32, vp]
+    lib.ob_flash_fwd_win_drop_bf16.argtypes = (
+        lib.ob_flash_fwd_win_bf16.argtypes[:-2] + drop_args)
+    lib.ob_flash_bwd_win_d_drop_bf16.argtypes = (
+        lib.ob_flash_bwd_win_d_bf16.argtypes[:-2] + drop_args)
+    lib.ob_flash_fwd_hd96_drop_bf16.argtypes = (
+        lib.ob_flash_fwd_win_drop_bf16.argtypes)
+    lib.ob_flash_bwd_hd96_d_drop_bf16.argtypes = (
+        lib.ob_flash_bwd_win_d_drop_bf16.argtypes)
     # deterministic mode (include/oobleck_stage.h)
     lib.ob_set_deterministic.argtypes = [i32]
     lib.ob_deterministic.argtypes = []
@@ -350,6 +361,7 @@ PLAN_DET, PLAN_BF16_FLASH, PLAN_FLASH_TR, PLAN_FLASH_DROP, PLAN_FLASH_HD128 = (
     1, 2, 4, 8, 16)
 PLAN_FLASH_HD128_DROP = 32  # OB_FLASH_HD128_DROP, off by default
 PLAN_FLASH_HD96 = 64  # OB_FLASH_HD96, off by default
+PLAN_FLASH_BAND_DROP = 128  # OB_FLASH_BAND_DROP, off by default
 
 
 def layer_plan(desc: ObLayerDesc, drop: ObDropoutDesc | None = None,

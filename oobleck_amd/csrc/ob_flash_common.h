@@ -149,7 +149,7 @@ __device__ __forceinline__ bf16x8 h96_tr_frag(const __bf16* tile, int lane,
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
-// Attention dropout (DESIGN.md §8 items 15 and 20).  The mask
+// Attention dropout (DESIGN.md §8 items 15, 20 and 23).  The mask
 // is ob_philox.h's, site OB_DROP_ATTN: element e = (z*S + q)*S + kv of the
 // full [B*nh, S, S] square, word e & 3 of ob_drop_words(key, e >> 2), and
 // ob_drop_factor's rule (word >= thr keeps, kept values times key.scale).

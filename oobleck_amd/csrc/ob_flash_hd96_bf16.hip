@@ -48,8 +48,29 @@
 // attributed __global__ wrappers for the reason given in
 // ob_flash_hd128_bf16.hip.  Resources: profiles/flash_hd96_resources.txt.
 //
-// Out of scope: dropout at these head sizes, the fp32 and materialized-P
-// banded routes.
+// Attention dropout (the mask definition and helpers are
+// ob_flash_common.h's).  Each body is also a template on kDrop, under a `_drop`
+// __global__ wrapper that takes the ob_drop_key by value; the kDrop = false
+// instantiations compile to the resources they had
+// (profiles/flash_band_drop_resources.txt).  m, l and the LSE come from the
+// undropped, masked P; the factor multiplies the PV operand only, in fp32 just
+// before bf_dance, so a masked P stays an exact 0 and bits drawn outside the
+// band are harmless.
+//   forward: the tile's 32 keep bits (drop_bits_q<8>, counter from the tile's
+//     true kv0) are drawn at the top of the iteration, before the staging
+//     loads, and only in the tiles the wave computes;
+//   dQ: a sub-tile's 16 bits (drop_bits_q<4>) just before its S and dP chains,
+//     inside the wave-uniform band test, so a skipped sub-tile draws nothing;
+//     dS = P * (f * dP - D);
+//   dK/dV: role 0 makes the quad-shared draw of the dense kernels (four Philox
+//     calls per lane, packed bits exchanged within the quad) at the top of an
+//     iteration its pair computes, and hands the keep bit to role 1 as the
+//     sign of the fp32 P it writes to xch (P >= 0, a masked P is +0 or -0 and
+//     multiplies to 0 either way); role 1 draws nothing.
+// At HD = 80 the factor multiplies P, never V: accumulator columns 80..95 keep
+// receiving zeros and every store still stops at column HD.
+//
+// Out of scope: the fp32 and materialized-P banded routes.
 #include "ob_flash_common.h"
 #include "ob_internal.h"
 #include "ob_flash_fold.h"
@@ -117,11 +138,11 @@ __device__ __forceinline__ void h96_zero_pad(__bf16* t, int rows, int tid) {
 // Forward.  Block: 4 waves x 32 q rows; 64-row kv tiles.
 // LDS: 2 x (K + V tile) x 64 x 96 x 2 B + bcast = 48.5 KB.
 // ===========================================================================
-template <int HD>
+template <int HD, bool kDrop>
 __device__ __forceinline__ void h96_fwd_body(
     const __bf16* __restrict__ qkv, __bf16* __restrict__ Obase,
     float* __restrict__ lse, int Sq, int H, int nh, int Z, int W,
-    float scale) {
+    float scale, const ob_drop_key& key) {
   constexpr int NS = HD / 16;
   __shared__ __attribute__((aligned(16))) __bf16 kbuf[2][64 * 96];
   __shared__ __attribute__((aligned(16))) __bf16 vbuf[2][64 * 96];
@@ -167,6 +188,10 @@ __device__ __forceinline__ void h96_fwd_body(
   for (int kvt = t_lo; kvt <= t_hi; ++kvt) {
     const int kv0 = kvt * 64;
     const int buf = (kvt - t_lo) & 1;
+    [[maybe_unused]] uint32_t keep = 0;  // bit 16u + r, as drop_bits_q
+    if constexpr (kDrop)
+      if (kvt >= w_lo && kvt <= w_hi)  // wave-uniform
+        keep = drop_bits_q(key, drop_crow(z, Sq, myq, kh) + (kv0 >> 2));
     if (kvt < t_hi)
       h96_stage2<HD, 64>(kbuf[buf ^ 1], Kp + (kv0 + 64) * ld, ld,
                          vbuf[buf ^ 1], Vp + (kv0 + 64) * ld, ld, tid);
@@ -238,6 +263,11 @@ __device__ __forceinline__ void h96_fwd_body(
       l += psum;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
+        if constexpr (kDrop) {
+#pragma unroll
+          for (int r = 8 * t; r < 8 * t + 8; ++r)
+            sv[r] *= drop_factor_bit(key, keep, r);
+        }
         const bf16x8 pa = bf_dance(sv + t * 8);
         // B[k = kv 16t+8kh..+7][n = d]: columns of the row-major V tile
 #pragma unroll
@@ -270,7 +300,15 @@ __global__ OB_HD96_KERNEL __launch_bounds__(256, 2) void k_flash_fwd_hd96(
     const __bf16* __restrict__ qkv, __bf16* __restrict__ Obase,
     float* __restrict__ lse, int Sq, int H, int nh, int Z, int W,
     float scale) {
-  h96_fwd_body<HD>(qkv, Obase, lse, Sq, H, nh, Z, W, scale);
+  h96_fwd_body<HD, false>(qkv, Obase, lse, Sq, H, nh, Z, W, scale,
+                          ob_drop_key{});
+}
+template <int HD>
+__global__ OB_HD96_KERNEL __launch_bounds__(256, 2) void k_flash_fwd_hd96_drop(
+    const __bf16* __restrict__ qkv, __bf16* __restrict__ Obase,
+    float* __restrict__ lse, int Sq, int H, int nh, int Z, int W, float scale,
+    ob_drop_key key) {
+  h96_fwd_body<HD, true>(qkv, Obase, lse, Sq, H, nh, Z, W, scale, key);
 }
 
 // ===========================================================================
@@ -281,13 +319,13 @@ __global__ OB_HD96_KERNEL __launch_bounds__(256, 2) void k_flash_fwd_hd96(
 // written to Dout for the dK/dV launch that follows.
 // LDS: 2 x (K + V tile) + red = 49.5 KB.
 // ===========================================================================
-template <int HD>
+template <int HD, bool kDrop>
 __device__ __forceinline__ void h96_dq_body(
     const __bf16* __restrict__ qkv, const __bf16* __restrict__ dO,
     const float* __restrict__ lse, const __bf16* __restrict__ O,
     float* __restrict__ Dout, __bf16* __restrict__ dqkv,
     float* __restrict__ dbias, int Sq, int H, int nh, int Z, int W,
-    float scale) {
+    float scale, const ob_drop_key& key) {
   constexpr int NS = HD / 16;
   __shared__ __attribute__((aligned(16))) __bf16 kbuf[2][64 * 96];
   __shared__ __attribute__((aligned(16))) __bf16 vbuf[2][64 * 96];
@@ -353,6 +391,10 @@ __device__ __forceinline__ void h96_dq_body(
       // wave-uniform: the sub-tile starts at or below the wave's last row
       // and ends inside the band of its first row
       if (kvu <= q0 + 31 && kvu + 31 > q0 - W) {
+        [[maybe_unused]] uint32_t keep = 0;  // bit r of this sub-tile
+        if constexpr (kDrop)
+          keep = drop_bits_q<4>(
+              key, drop_crow(z, Sq, myq, kh) + (kv0 >> 2) + 8 * u);
         f32x16 sa = {}, pa = {};
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
@@ -371,14 +413,20 @@ __device__ __forceinline__ void h96_dq_body(
         // sub-tile (all of it inside the band of all 32 rows): no mask
         if (kvu + 31 <= q0 && kvu > q0 + 31 - W) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r)
-            dsv[r] = __expf(sa[r] * scale - mylse) * (pa[r] - myD);
+          for (int r = 0; r < 16; ++r) {
+            // kDrop: dS = P * (f * dP - D)
+            float dp = pa[r];
+            if constexpr (kDrop) dp *= drop_factor_bit(key, keep, r);
+            dsv[r] = __expf(sa[r] * scale - mylse) * (dp - myD);
+          }
         } else {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const bool ok =
                 (unsigned)(myq - (kvu + acc_row(r, kh))) < (unsigned)W;
-            dsv[r] = ok ? __expf(sa[r] * scale - mylse) * (pa[r] - myD) : 0.f;
+            float dp = pa[r];
+            if constexpr (kDrop) dp *= drop_factor_bit(key, keep, r);
+            dsv[r] = ok ? __expf(sa[r] * scale - mylse) * (dp - myD) : 0.f;
           }
         }
 #pragma unroll
@@ -429,7 +477,20 @@ __global__ OB_HD96_KERNEL __launch_bounds__(256, 2) void k_flash_bwd_dq_hd96(
     float* __restrict__ Dout, __bf16* __restrict__ dqkv,
     float* __restrict__ dbias, int Sq, int H, int nh, int Z, int W,
     float scale) {
-  h96_dq_body<HD>(qkv, dO, lse, O, Dout, dqkv, dbias, Sq, H, nh, Z, W, scale);
+  h96_dq_body<HD, false>(qkv, dO, lse, O, Dout, dqkv, dbias, Sq, H, nh, Z, W,
+                         scale, ob_drop_key{});
+}
+template <int HD>
+__global__ OB_HD96_KERNEL __launch_bounds__(256, 2) void
+k_flash_bwd_dq_hd96_drop(const __bf16* __restrict__ qkv,
+                         const __bf16* __restrict__ dO,
+                         const float* __restrict__ lse,
+                         const __bf16* __restrict__ O,
+                         float* __restrict__ Dout, __bf16* __restrict__ dqkv,
+                         float* __restrict__ dbias, int Sq, int H, int nh,
+                         int Z, int W, float scale, ob_drop_key key) {
+  h96_dq_body<HD, true>(qkv, dO, lse, O, Dout, dqkv, dbias, Sq, H, nh, Z, W,
+                        scale, key);
 }
 
 // ===========================================================================
@@ -442,12 +503,12 @@ __global__ OB_HD96_KERNEL __launch_bounds__(256, 2) void k_flash_bwd_dq_hd96(
 // B operands here.
 // LDS: xch 16 KB + 2 x (Q + dO tile) x 32 x 96 x 2 B + red = 41.5 KB.
 // ===========================================================================
-template <int HD>
+template <int HD, bool kDrop>
 __device__ __forceinline__ void h96_dkdv_body(
     const __bf16* __restrict__ qkv, const __bf16* __restrict__ dO,
     const float* __restrict__ lse, const float* __restrict__ D,
     __bf16* __restrict__ dqkv, float* __restrict__ dbias, int Sq, int H,
-    int nh, int Z, int W, float scale) {
+    int nh, int Z, int W, float scale, const ob_drop_key& key) {
   constexpr int NS = HD / 16;
   __shared__ float xch[2][2][32 * 32];  // [buffer][pair][P tile]
   __shared__ __attribute__((aligned(16))) __bf16 qbuf[2][32 * 96];
@@ -494,6 +555,34 @@ __device__ __forceinline__ void h96_dkdv_body(
   f32x16 acc[3] = {};  // role 0: dV d groups; role 1: dK d groups
   for (int qt = qt_lo; qt <= qt_hi; ++qt) {
     const int q0 = qt * 32;
+    // bit r: keep of element r (q row q0 + acc_row(r, kh), column mykv)
+    [[maybe_unused]] uint32_t keep = 0;
+    if constexpr (kDrop) {
+      if (role == 0 && qt >= p_lo && qt <= p_hi) {  // wave-uniform
+        // Philox counter of q row q0 + 4*kh at this lane's kv quad
+        const uint32_t sq4 = (uint32_t)(Sq >> 2);
+        const uint32_t c0 = (uint32_t)(z * Sq + q0 + 4 * kh) * sq4 +
+                            (uint32_t)(mykv >> 2);
+        uint32_t mine = 0;  // rows r = 4g + (il & 3): bit 4g + word
+#pragma unroll 1
+        for (int g = 0; g < 4; ++g) {
+          const ob_philox4 w4 =
+              ob_drop_words(key, c0 + (uint32_t)((il & 3) + 8 * g) * sq4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            mine |= (uint32_t)(w4.w[j] >= key.thr) << (4 * g + j);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          // quad lane j drew rows 4g + j; take this lane's word of each
+          const uint32_t theirs =
+              (uint32_t)__shfl((int)mine, (lane & ~3) | j, 64) >> (il & 3);
+#pragma unroll
+          for (int g = 0; g < 4; ++g)
+            keep |= ((theirs >> (4 * g)) & 1u) << (4 * g + j);
+        }
+      }
+    }
     if (qt < qt_hi)
       h96_stage2<HD, 32>(qbuf[(qt + 1) & 1], Qp + (q0 + 32) * ld, ld,
                          obuf[(qt + 1) & 1], dOp + (int64_t)(q0 + 32) * H, H,
@@ -536,7 +625,14 @@ __device__ __forceinline__ void h96_dkdv_body(
             inner || (unsigned)(q0 + qoff - mykv) < (unsigned)W;
         const float lse_q = __shfl(lse_t, qoff, 64);
         pv[r] = ok ? __expf(own[r] * scale - lse_q) : 0.f;
-        ptile[qoff * 32 + il] = pv[r];
+        if constexpr (kDrop) {
+          // the keep bit rides to role 1 as the sign of P (P >= 0)
+          const bool kept = (keep >> r) & 1u;
+          ptile[qoff * 32 + il] = kept ? pv[r] : -pv[r];
+          pv[r] = kept ? pv[r] * key.scale : 0.f;
+        } else {
+          ptile[qoff * 32 + il] = pv[r];
+        }
       }
     }
     __syncthreads();
@@ -547,7 +643,14 @@ __device__ __forceinline__ void h96_dkdv_body(
         const int qoff = acc_row(r, kh);
         const float d_q = __shfl(d_t, qoff, 64);
         // dS = P * (dP - D); masked entries have P == 0 already
-        pv[r] = ptile[qoff * 32 + il] * (own[r] - d_q);
+        if constexpr (kDrop) {
+          // dS = P * (f * dP - D): |x| is P, a set sign bit says dropped
+          const float x = ptile[qoff * 32 + il];
+          const float f = __builtin_signbit(x) ? 0.f : key.scale;
+          pv[r] = __builtin_fabsf(x) * (f * own[r] - d_q);
+        } else {
+          pv[r] = ptile[qoff * 32 + il] * (own[r] - d_q);
+        }
       }
     }
 #pragma unroll
@@ -594,7 +697,20 @@ __global__ OB_HD96_KERNEL __launch_bounds__(256, 2) void k_flash_bwd_dkdv_hd96(
     const float* __restrict__ lse, const float* __restrict__ D,
     __bf16* __restrict__ dqkv, float* __restrict__ dbias, int Sq, int H,
     int nh, int Z, int W, float scale) {
-  h96_dkdv_body<HD>(qkv, dO, lse, D, dqkv, dbias, Sq, H, nh, Z, W, scale);
+  h96_dkdv_body<HD, false>(qkv, dO, lse, D, dqkv, dbias, Sq, H, nh, Z, W,
+                           scale, ob_drop_key{});
+}
+template <int HD>
+__global__ OB_HD96_KERNEL __launch_bounds__(256, 2) void
+k_flash_bwd_dkdv_hd96_drop(const __bf16* __restrict__ qkv,
+                           const __bf16* __restrict__ dO,
+                           const float* __restrict__ lse,
+                           const float* __restrict__ D,
+                           __bf16* __restrict__ dqkv,
+                           float* __restrict__ dbias, int Sq, int H, int nh,
+                           int Z, int W, float scale, ob_drop_key key) {
+  h96_dkdv_body<HD, true>(qkv, dO, lse, D, dqkv, dbias, Sq, H, nh, Z, W,
+                          scale, key);
 }
 
 // ---- entries ----------------------------------------------------------------
@@ -679,4 +795,105 @@ extern "C" int ob_flash_bwd_hd96_d_bf16(const void* qkv, const void* O,
                                 H, nh, W, scale, stream)
                   : h96_bwd<96>(qkv, O, dO, lse, D_ws, dqkv, dbias_qkv, B, Sq,
                                 H, nh, W, scale, stream);
+}
+
+// ---- entries with attention dropout ------------------
+// the plain entry's checks, then p and the mask's element count; 80 or 96, 0
+// with ob_fail set
+static int h96_drop_head_dim(const char* who, int64_t B, int64_t Sq, int64_t H,
+                             int64_t nh, int64_t window, float p) {
+  const int hd = h96_head_dim(who, B, Sq, H, nh, window);
+  if (!hd) return 0;
+  if (!ob_drop_p_ok(p)) {
+    ob_fail("%s: p must be in [0,1)", who);
+    return 0;
+  }
+  if (B * nh * Sq * Sq > ((int64_t)1 << 34)) {
+    ob_fail("%s: B*nh*S*S exceeds the 2^34 mask elements", who);
+    return 0;
+  }
+  return hd;
+}
+
+template <int HD>
+static int h96_fwd_drop(const void* qkv, void* O, void* lse, int64_t B,
+                        int64_t Sq, int64_t H, int64_t nh, int W, float scale,
+                        const ob_drop_key& key, void* stream) {
+  const int Z = (int)(B * nh);
+  k_flash_fwd_hd96_drop<HD>
+      <<<ob_fold_grid((int)Sq / 128, Z), 256, 0, S(stream)>>>(
+          (const __bf16*)qkv, (__bf16*)O, (float*)lse, (int)Sq, (int)H,
+          (int)nh, Z, W, scale, key);
+  OB_LAUNCH_CHECK();
+  return 0;
+}
+
+// ob_flash_fwd_hd96_bf16 with attention dropout (site OB_DROP_ATTN) applied
+// to P before PV; p == 0 is the plain entry.
+extern "C" int ob_flash_fwd_hd96_drop_bf16(const void* qkv, void* O, void* lse,
+                                           int64_t B, int64_t Sq, int64_t H,
+                                           int64_t nh, int64_t window,
+                                           float scale, uint64_t seed,
+                                           int32_t layer_id, uint64_t tick,
+                                           float p, void* stream) {
+  const int hd =
+      h96_drop_head_dim("flash_fwd_hd96_drop", B, Sq, H, nh, window, p);
+  if (!hd) return 1;
+  if (p == 0.f)
+    return ob_flash_fwd_hd96_bf16(qkv, O, lse, B, Sq, H, nh, window, scale,
+                                  stream);
+  const ob_drop_key key =
+      ob_drop_make_key(seed, layer_id, OB_DROP_ATTN, tick, p);
+  const int W = h96_window(window, Sq);
+  return hd == 80
+             ? h96_fwd_drop<80>(qkv, O, lse, B, Sq, H, nh, W, scale, key,
+                                stream)
+             : h96_fwd_drop<96>(qkv, O, lse, B, Sq, H, nh, W, scale, key,
+                                stream);
+}
+
+// dq first (forms D from O and dO into D_ws), then dkdv, which reads it
+template <int HD>
+static int h96_bwd_drop(const void* qkv, const void* O, const void* dO,
+                        const void* lse, void* D_ws, void* dqkv,
+                        void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
+                        int64_t nh, int W, float scale, const ob_drop_key& key,
+                        void* stream) {
+  const int Z = (int)(B * nh);
+  k_flash_bwd_dq_hd96_drop<HD>
+      <<<ob_fold_grid((int)Sq / 128, Z), 256, 0, S(stream)>>>(
+          (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse,
+          (const __bf16*)O, (float*)D_ws, (__bf16*)dqkv, (float*)dbias_qkv,
+          (int)Sq, (int)H, (int)nh, Z, W, scale, key);
+  OB_LAUNCH_CHECK();
+  k_flash_bwd_dkdv_hd96_drop<HD>
+      <<<ob_fold_grid((int)Sq / 64, Z), 256, 0, S(stream)>>>(
+          (const __bf16*)qkv, (const __bf16*)dO, (const float*)lse,
+          (const float*)D_ws, (__bf16*)dqkv, (float*)dbias_qkv, (int)Sq,
+          (int)H, (int)nh, Z, W, scale, key);
+  OB_LAUNCH_CHECK();
+  return 0;
+}
+
+// ob_flash_bwd_hd96_d_bf16 for a forward that ran ob_flash_fwd_hd96_drop_bf16
+// with the same key; p == 0 is the plain entry.
+extern "C" int ob_flash_bwd_hd96_d_drop_bf16(
+    const void* qkv, const void* O, const void* dO, const void* lse,
+    void* D_ws, void* dqkv, void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
+    int64_t nh, int64_t window, float scale, uint64_t seed, int32_t layer_id,
+    uint64_t tick, float p, void* stream) {
+  const int hd =
+      h96_drop_head_dim("flash_bwd_hd96_d_drop", B, Sq, H, nh, window, p);
+  if (!hd) return 1;
+  if (p == 0.f)
+    return ob_flash_bwd_hd96_d_bf16(qkv, O, dO, lse, D_ws, dqkv, dbias_qkv, B,
+                                    Sq, H, nh, window, scale, stream);
+  const ob_drop_key key =
+      ob_drop_make_key(seed, layer_id, OB_DROP_ATTN, tick, p);
+  const int W = h96_window(window, Sq);
+  return hd == 80
+             ? h96_bwd_drop<80>(qkv, O, dO, lse, D_ws, dqkv, dbias_qkv, B, Sq,
+                                H, nh, W, scale, key, stream)
+             : h96_bwd_drop<96>(qkv, O, dO, lse, D_ws, dqkv, dbias_qkv, B, Sq,
+                                H, nh, W, scale, key, stream);
 }

@@ -304,20 +304,26 @@ static bool no_blaslt() {
 // attn_pdrop > 0 take the flash kernels' dropout variants
 // (ob_flash_*_drop_hd128_bf16) instead of that path.  OB_FLASH_HD96=1
 // (default 0) lets a head_dim 80 or 96 layer with attn_pdrop == 0 take the
-// kernels of ob_flash_hd96_bf16.hip, dense or banded.  All read once.
+// kernels of ob_flash_hd96_bf16.hip, dense or banded.
+// OB_FLASH_BAND_DROP=1 (default 0) lets a banded layer, and a head_dim 80 or
+// 96 layer, with attn_pdrop > 0 take the dropout variants of the banded and
+// hd96 kernels (ob_flash_*_win_drop_bf16, ob_flash_*_hd96_drop_bf16).  All
+// read once.
 static ob_layer_modes process_modes() {
   static const bool fl = ob_env_flag("OB_BF16_FLASH", true),
                     drop = ob_env_flag("OB_FLASH_DROP", true),
                     hd128 = ob_env_flag("OB_FLASH_HD128", true),
                     hd128_drop = ob_env_flag("OB_FLASH_HD128_DROP", false),
-                    hd96 = ob_env_flag("OB_FLASH_HD96", false);
+                    hd96 = ob_env_flag("OB_FLASH_HD96", false),
+                    band_drop = ob_env_flag("OB_FLASH_BAND_DROP", false);
   return {ob_deterministic() != 0, fl, flash_tr(), drop, hd128, hd128_drop,
-          hd96};
+          hd96, band_drop};
 }
 static ob_layer_modes modes_of_bits(int bits) {
   if (bits < 0) return process_modes();
   return {(bits & 1) != 0, (bits & 2) != 0, (bits & 4) != 0, (bits & 8) != 0,
-          (bits & 16) != 0, (bits & 32) != 0, (bits & 64) != 0};
+          (bits & 16) != 0, (bits & 32) != 0, (bits & 64) != 0,
+          (bits & 128) != 0};
 }
 
 // the decision ob_layer_create_ex takes for `d` with this attn_pdrop; host
@@ -876,7 +882,16 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   if (l->plan.flash && flash_tr()) {
     // the fused kernel writes O and the per-row LSE (stored where the
     // materialized-P path keeps P)
-    if (dA) {
+    if (dA && (hd == 80 || hd == 96 || ob_plan_windowed(l->d))) {
+      // the plan admits these with OB_FLASH_BAND_DROP=1 only
+      const auto fwd_drop = hd == 80 || hd == 96 ? ob_flash_fwd_hd96_drop_bf16
+                                                 : ob_flash_fwd_win_drop_bf16;
+      if (OB_PROF(OB_PF_FLASH_FWD, stream,
+                  fwd_drop(s.qkv, s.am, s.lseP, B, Sq, H, nh, l->d.attn_window,
+                           1.f / sqrtf((float)hd), l->seed, l->layer_id,
+                           l->slot_tick[slot], l->p_attn, stream)))
+        return 1;
+    } else if (dA) {
       // attention dropout inside the kernel: masks of this slot's tick
       const auto fwd_drop = hd == 128 ? ob_flash_fwd_drop_hd128_bf16
                                       : ob_flash_fwd_nt_drop_bf16;
@@ -1109,7 +1124,17 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     // also adds the b_qkv grad (column sums of DQKV) from its accumulators
     // (deterministic mode: not asked for; the side-stream colsum below)
     float* const dbq = det ? nullptr : g + bp.b_qkv;
-    if (dA) {
+    if (dA && (hd == 80 || hd == 96 || ob_plan_windowed(l->d))) {
+      const auto bwd_drop = hd == 80 || hd == 96
+                                ? ob_flash_bwd_hd96_d_drop_bf16
+                                : ob_flash_bwd_win_d_drop_bf16;
+      if (OB_PROF(OB_PF_FLASH_BWD, stream,
+                  bwd_drop(s.qkv, s.am, w.DATT, s.lseP, w.D, w.DQKV, dbq, B,
+                           Sq, H, nh, l->d.attn_window, scale, l->seed,
+                           l->layer_id, l->slot_tick[slot], l->p_attn,
+                           stream)))
+        return 1;
+    } else if (dA) {
       // regenerates the masks the forward of this slot drew
       const auto bwd_drop = hd == 128 ? ob_flash_bwd_d_drop_hd128_bf16
                                       : ob_flash_bwd_nt_d_drop_bf16;

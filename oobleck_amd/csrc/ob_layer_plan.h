@@ -59,6 +59,7 @@ struct ob_layer_modes {
   bool det, bf16_flash, flash_tr, flash_drop, flash_hd128;
   bool flash_hd128_drop;  // OB_FLASH_HD128_DROP, off by default
   bool flash_hd96;        // OB_FLASH_HD96, off by default
+  bool flash_band_drop;   // OB_FLASH_BAND_DROP, off by default
 };
 
 struct ob_layer_plan {
@@ -92,15 +93,19 @@ inline int64_t ob_v_pad(int64_t V) { return (V + 255) / 256 * 256; }
 // kernels are production-only and have no dropout variants.
 // A banded layer (ob_plan_windowed) is a flash layer under the same
 // conditions plus attn_pdrop == 0 and flash_tr: the banded kernels
-// (ob_flash_win_bf16.hip, ob_flash_hd96_bf16.hip) are production-only and
-// have no dropout variants.
+// (ob_flash_win_bf16.hip, ob_flash_hd96_bf16.hip) are production-only.
+// flash_band_drop (off by default) admits attn_pdrop > 0 where the two
+// paragraphs above refuse it: a banded layer, and head_dim 80 or 96 dense or
+// banded, through the `_drop` variants of those two files' kernels.  Such a
+// layer's plan is its p = 0 flash plan.
 inline bool ob_plan_windowed(const ob_layer_desc& d) {
   return d.kind == OB_KIND_BLOCK && d.attn_window > 0 &&
          d.attn_window < d.seq_len;
 }
 inline bool ob_plan_flash(const ob_layer_desc& d, float p_attn,
                           const ob_layer_modes& m) {
-  if (ob_plan_windowed(d) && (p_attn > 0.f || !m.flash_tr)) return false;
+  const bool p_ok = p_attn == 0.f || m.flash_band_drop;  // > 0: see below
+  if (ob_plan_windowed(d) && !(p_ok && m.flash_tr)) return false;
   if (p_attn > 0.f && !(m.flash_tr && m.flash_drop)) return false;
   if (!m.bf16_flash || d.kind != OB_KIND_BLOCK || d.dtype != 1 ||
       d.n_head <= 0 || d.n_embd % d.n_head || d.seq_len <= 0 ||
@@ -109,9 +114,9 @@ inline bool ob_plan_flash(const ob_layer_desc& d, float p_attn,
   const int64_t hd = d.n_embd / d.n_head;
   if (hd == 128)
     return m.flash_tr && m.flash_hd128 &&
-           (p_attn == 0.f || m.flash_hd128_drop);  // > 0: flash_drop is on
-  if (hd == 80 || hd == 96)
-    return m.flash_hd96 && m.flash_tr && p_attn == 0.f;
+           (p_attn == 0.f || m.flash_hd128_drop ||  // > 0: flash_drop is on
+            (m.flash_band_drop && ob_plan_windowed(d)));
+  if (hd == 80 || hd == 96) return m.flash_hd96 && m.flash_tr && p_ok;
   return hd == 64;
 }
 
@@ -144,7 +149,8 @@ inline ob_layer_plan ob_layer_plan_of(const ob_layer_desc& d, float p_resid,
         p.error =
             "0 < attn_window < seq_len needs a flash layer: bf16, head_dim "
             "64 or 128 (80 or 96 with OB_FLASH_HD96=1), seq_len % 128 == 0, "
-            "attn_pdrop == 0, and none of OB_BF16_FLASH=0, OB_FLASH_TR=0, "
+            "attn_pdrop == 0 (> 0 with OB_FLASH_BAND_DROP=1 and not "
+            "OB_FLASH_DROP=0), and none of OB_BF16_FLASH=0, OB_FLASH_TR=0, "
             "OB_FLASH_HD128=0 (head_dim 128)";
       st(ST_X, BSH), st(ST_MEAN1, BS), st(ST_RSTD1, BS), st(ST_LN1, BSH);
       st(ST_QKV, 3 * BSH), st(ST_P, p.flash ? Bm * nh * Sq : PSS);

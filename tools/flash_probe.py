@@ -33,6 +33,12 @@
 # without --window it prints --repeats repeats of the dense forward and
 # backward with min / max and TF; with --window the A/B above (plus the TF of
 # both arms' minima: causal FLOPs times band / triangle for the window arm).
+#
+# --attn-pdrop P together with --window W, or with --head-dim 80 / 96 (then
+# also without a window: the dense arm), times the dropout entries of those
+# kernels (ob_flash_*_win_drop_bf16 / ob_flash_*_hd96_drop_bf16) against the
+# plain ones at the same window: the A/B above with the arms "plain" and
+# "drop", and drop / plain of the minima.
 import argparse
 import ctypes
 import pathlib
@@ -199,6 +205,49 @@ def timeit_once(fn, reps=30):
     torch.cuda.synchronize()
     return st.elapsed_time(en) / reps * 1e3
 
+
+if args.attn_pdrop > 0.0 and (args.window or hd in (80, 96)):
+    W = args.window
+    assert 0 <= W < S, "--window must be in (0, S)"
+    fam = "hd96" if hd in (80, 96) else "win"
+    key = (*DROP_KEY, args.attn_pdrop)
+
+    def arm(drop):
+        f = getattr(ext, f"ob_flash_fwd_{fam}{'_drop' * drop}_bf16")
+        b = getattr(ext, f"ob_flash_bwd_{fam}_d{'_drop' * drop}_bf16")
+        tail = (W, scale) + (key if drop else ()) + (stream(),)
+        return (lambda: check(f(ptr(qkv), ptr(O), ptr(lse), B, S, H, nh,
+                                *tail)),
+                lambda: check(b(ptr(qkv), ptr(O), ptr(dO), ptr(lse),
+                                ptr(D_ws), ptr(dqkv), ptr(dbias), B, S, H, nh,
+                                *tail)))
+
+    (fwd_p, bwd_p), (fwd_d, bwd_d) = arm(0), arm(1)
+    print(f"head_dim {hd}, (B, nh, S) = ({B}, {nh}, {S}), window {W or 'none'}"
+          f", attn_pdrop {args.attn_pdrop}")
+    # each backward reads the O and lse of its own arm's forward
+    for name, plain, drop, pre in (
+            ("fwd", fwd_p, fwd_d, (None, None)),
+            ("bwd (dq + dkdv, D in-kernel, + bias)", bwd_p, bwd_d,
+             (fwd_p, fwd_d))):
+        for fn in (plain, drop):
+            for _ in range(5):
+                fn()
+        torch.cuda.synchronize()
+        us = ([], [])
+        for _ in range(args.repeats):
+            for a, fn in enumerate((plain, drop)):
+                if pre[a]:
+                    pre[a]()
+                us[a].append(timeit_once(fn))
+        p_, d_ = us
+        print(f"{name}")
+        print("  plain us: " + " ".join(f"{v:7.1f}" for v in p_))
+        print("  drop  us: " + " ".join(f"{v:7.1f}" for v in d_))
+        print(f"  plain min {min(p_):.1f} max {max(p_):.1f}; drop min "
+              f"{min(d_):.1f} max {max(d_):.1f}; drop / plain = "
+              f"{min(d_) / min(p_):.2f}")
+    sys.exit(0)
 
 if args.window:
     W = args.window
