@@ -75,6 +75,14 @@ typedef struct {
                            attn_pdrop == 0 unless OB_FLASH_BAND_DROP=1, else
                            the create fails.  A
                            zero-filled or keyword-built description is dense */
+  int32_t attn_bidir;   /* BLOCK: 0 = causal attention, what a zero-filled or
+                           keyword-built description gets.  Nonzero: every
+                           query sees every key (ob_flash_*_bidir_*bf16), the
+                           attention of an encoder block.  Such a layer must
+                           be a flash layer: bf16, head_dim 64, seq_len % 128
+                           == 0, attn_pdrop == 0, attn_window 0 or >= seq_len,
+                           and neither OB_BF16_FLASH=0 nor OB_FLASH_TR=0; else
+                           the create fails */
 } ob_layer_desc;
 
 /* Number of fp32 elements in the layer's flat parameter buffer.  Layout is
@@ -129,8 +137,9 @@ int ob_layer_create_ex(const ob_layer_desc* desc, const ob_dropout_desc* drop,
  * OB_FLASH_DROP=0; head_dim 80 or 96 only with OB_FLASH_HD96=1 (default 0),
  * attn_pdrop == 0 and not OB_FLASH_TR=0; with OB_FLASH_BAND_DROP=1 (default
  * 0) and not OB_FLASH_DROP=0, attn_pdrop > 0 is also taken at head_dim 80 or
- * 96 and by a banded layer of any of the four head sizes), 0 otherwise.
- * Host-only. */
+ * 96 and by a banded layer of any of the four head sizes; a layer with
+ * attn_bidir set only under the conditions listed at that field), 0
+ * otherwise.  Host-only. */
 int ob_layer_uses_flash(ob_layer_t l);
 /* The same decision for a description, before any layer exists: what
  * ob_layer_create_ex will take for `desc` with this attn_pdrop.  Host-only,
@@ -562,7 +571,22 @@ int ob_flash_bwd_hd96_d_drop_bf16(const void* qkv, const void* O,
                                   int64_t window, float scale, uint64_t seed,
                                   int32_t layer_id, uint64_t tick, float p,
                                   void* stream);
-/* Host-only queries of the block -> work mapping of the three kernels above
+/* Bidirectional (non-causal) flash attention: every query row attends every
+ * key, no mask.  Kernels of their own (ob_flash_bidir_bf16.hip, DESIGN.md item
+ * 24) whose blocks own consecutive rows and visit every tile.  bf16, head_dim
+ * 64 only (H == 64 * nh), Sq % 128 == 0, positive sizes; the buffers, LSE,
+ * D_ws and dbias_qkv contracts of ob_flash_fwd_nt_bf16 /
+ * ob_flash_bwd_nt_d_bf16: the backward runs dq (forming D into D_ws) first,
+ * then dkdv; a null dbias_qkv skips the bias sum.  Any other shape returns 1
+ * with the error set and launches nothing.  No dropout, no window. */
+int ob_flash_fwd_bidir_bf16(const void* qkv, void* O, void* lse, int64_t B,
+                            int64_t Sq, int64_t H, int64_t nh, float scale,
+                            void* stream);
+int ob_flash_bwd_bidir_d_bf16(const void* qkv, const void* O, const void* dO,
+                              const void* lse, void* D_ws, void* dqkv,
+                              void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
+                              int64_t nh, float scale, void* stream);
+/* Host-only queries of the block -> work mapping of the three causal kernels
  * (no GPU call).  kind: 0 forward, 1 dq, 2 dkdv.
  * rows: unit = wave 0..3 (forward, dq) or wave pair 0..1 (dkdv) of `block`
  *   -> the first of its 32 rows and the tile range it computes; unit = -1 ->

@@ -25,6 +25,7 @@ class ObLayerDesc(ctypes.Structure):
         ("n_slots", ctypes.c_int32),
         ("dtype", ctypes.c_int32),
         ("attn_window", ctypes.c_int32),  # 0 = dense (the default)
+        ("attn_bidir", ctypes.c_int32),  # 0 = causal (the default)
     ]
 
 
@@ -195,6 +196,10 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
         lib.ob_flash_fwd_win_bf16.argtypes)
     lib.ob_flash_bwd_hd96_d_bf16.argtypes = (
         lib.ob_flash_bwd_win_d_bf16.argtypes)
+    # bidirectional (no mask): the dense argument lists
+    lib.ob_flash_fwd_bidir_bf16.argtypes = lib.ob_flash_fwd_nt_bf16.argtypes
+    lib.ob_flash_bwd_bidir_d_bf16.argtypes = (
+        lib.ob_flash_bwd_nt_d_bf16.argtypes)
     # (seed, layer_id, tick, p): the site is always DROP_ATTN
     lib.ob_flash_fwd_nt_drop_bf16.argtypes = [vp, vp, vp, i64, i64, i64, i64,
                                               f32, u64, i32, u64, f32, vp]

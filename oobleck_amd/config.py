@@ -28,6 +28,10 @@ class ModelConfig:
     # order), every=1 bands every block.
     attn_window: int = 0
     attn_window_every: int = 2
+    # False: every block's attention is bidirectional (no causal mask), the
+    # attention of an encoder (Megatron-BERT, ViT).  bf16 flash layers at
+    # head_dim 64 with attn_pdrop == 0 and no window only.
+    attn_causal: bool = True
 
     @property
     def n_layers_total(self) -> int:

@@ -882,7 +882,14 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   if (l->plan.flash && flash_tr()) {
     // the fused kernel writes O and the per-row LSE (stored where the
     // materialized-P path keeps P)
-    if (dA && (hd == 80 || hd == 96 || ob_plan_windowed(l->d))) {
+    if (ob_plan_bidir(l->d)) {
+      // bidirectional layer (the plan admits it at head_dim 64 with
+      // attn_pdrop == 0 and no band only)
+      if (OB_PROF(OB_PF_FLASH_FWD, stream,
+                  ob_flash_fwd_bidir_bf16(s.qkv, s.am, s.lseP, B, Sq, H, nh,
+                                          1.f / sqrtf((float)hd), stream)))
+        return 1;
+    } else if (dA && (hd == 80 || hd == 96 || ob_plan_windowed(l->d))) {
       // the plan admits these with OB_FLASH_BAND_DROP=1 only
       const auto fwd_drop = hd == 80 || hd == 96 ? ob_flash_fwd_hd96_drop_bf16
                                                  : ob_flash_fwd_win_drop_bf16;
@@ -1124,7 +1131,13 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     // also adds the b_qkv grad (column sums of DQKV) from its accumulators
     // (deterministic mode: not asked for; the side-stream colsum below)
     float* const dbq = det ? nullptr : g + bp.b_qkv;
-    if (dA && (hd == 80 || hd == 96 || ob_plan_windowed(l->d))) {
+    if (ob_plan_bidir(l->d)) {
+      if (OB_PROF(OB_PF_FLASH_BWD, stream,
+                  ob_flash_bwd_bidir_d_bf16(s.qkv, s.am, w.DATT, s.lseP, w.D,
+                                            w.DQKV, dbq, B, Sq, H, nh, scale,
+                                            stream)))
+        return 1;
+    } else if (dA && (hd == 80 || hd == 96 || ob_plan_windowed(l->d))) {
       const auto bwd_drop = hd == 80 || hd == 96
                                 ? ob_flash_bwd_hd96_d_drop_bf16
                                 : ob_flash_bwd_win_d_drop_bf16;

@@ -98,12 +98,23 @@ inline int64_t ob_v_pad(int64_t V) { return (V + 255) / 256 * 256; }
 // paragraphs above refuse it: a banded layer, and head_dim 80 or 96 dense or
 // banded, through the `_drop` variants of those two files' kernels.  Such a
 // layer's plan is its p = 0 flash plan.
+// A bidirectional layer (ob_plan_bidir; ob_flash_bidir_bf16.hip) is a flash
+// layer at head_dim 64 only, with attn_pdrop == 0, no band and flash_tr: those
+// kernels are production-only and have neither dropout nor banded variants.
+// Its plan is the causal flash plan of the same description.
 inline bool ob_plan_windowed(const ob_layer_desc& d) {
   return d.kind == OB_KIND_BLOCK && d.attn_window > 0 &&
          d.attn_window < d.seq_len;
 }
+inline bool ob_plan_bidir(const ob_layer_desc& d) {
+  return d.kind == OB_KIND_BLOCK && d.attn_bidir != 0;
+}
 inline bool ob_plan_flash(const ob_layer_desc& d, float p_attn,
                           const ob_layer_modes& m) {
+  if (ob_plan_bidir(d) &&
+      !(p_attn == 0.f && m.flash_tr && !ob_plan_windowed(d) &&
+        d.attn_window >= 0 && d.n_head > 0 && d.n_embd == 64 * d.n_head))
+    return false;
   const bool p_ok = p_attn == 0.f || m.flash_band_drop;  // > 0: see below
   if (ob_plan_windowed(d) && !(p_ok && m.flash_tr)) return false;
   if (p_attn > 0.f && !(m.flash_tr && m.flash_drop)) return false;
@@ -145,6 +156,11 @@ inline ob_layer_plan ob_layer_plan_of(const ob_layer_desc& d, float p_resid,
       // the materialized-P route has no band
       if (d.attn_window < 0)
         p.error = "attn_window must be >= 0";
+      else if (ob_plan_bidir(d) && !p.flash)
+        p.error =
+            "attn_bidir needs a flash layer: bf16, head_dim 64, seq_len % 128 "
+            "== 0, attn_pdrop == 0, attn_window 0 or >= seq_len, and neither "
+            "OB_BF16_FLASH=0 nor OB_FLASH_TR=0";
       else if (ob_plan_windowed(d) && !p.flash)
         p.error =
             "0 < attn_window < seq_len needs a flash layer: bf16, head_dim "

@@ -51,14 +51,19 @@ class Layer:
                  dtype: str = "f32", embd_pdrop: float | None = None,
                  resid_pdrop: float | None = None,
                  attn_pdrop: float | None = None, dropout_seed: int = 0,
-                 attn_window: int | None = None):
+                 attn_window: int | None = None,
+                 attn_causal: bool | None = None):
         """Dropout: the three probabilities default to the ModelConfig's;
         with all of them 0 the layer is created by ob_layer_create and is
         exactly the dropout-free layer.  Masks are stateless functions of
         (dropout_seed, layer_id, site, tick, element) — see forward_slot.
         attn_window: None takes cfg.layer_attn_window(layer_id); W > 0 makes
         a BLOCK's attention locally banded (flash-eligible bf16 layers with
-        attn_pdrop == 0 only: anything else fails in the create)."""
+        attn_pdrop == 0 only: anything else fails in the create).
+        attn_causal: None takes cfg.attn_causal; False makes a BLOCK's
+        attention bidirectional (flash-eligible bf16 layers at head_dim 64
+        with attn_pdrop == 0 and no window only: anything else fails in the
+        create)."""
         self.layer_id = layer_id
         self.cfg = cfg
         self.kind = cfg.layer_kind(layer_id)
@@ -69,12 +74,16 @@ class Layer:
         if attn_window is None:
             attn_window = cfg.layer_attn_window(layer_id)
         self.attn_window = int(attn_window)
+        if attn_causal is None:
+            attn_causal = cfg.attn_causal
+        self._attn_causal = bool(attn_causal)
         ext = get_ext()
         self._desc = ObLayerDesc(
             kind=self.kind, n_embd=cfg.n_embd, n_head=cfg.n_head,
             n_positions=cfg.n_positions, vocab_size=cfg.vocab_size,
             max_batch=max_batch, seq_len=seq_len, n_slots=n_slots,
-            dtype=0 if dtype == "f32" else 1, attn_window=self.attn_window)
+            dtype=0 if dtype == "f32" else 1, attn_window=self.attn_window,
+            attn_bidir=0 if self._attn_causal else 1)
         n = ext.ob_layer_param_count(ctypes.byref(self._desc))
         assert n > 0
         init = init_layer_params(cfg, layer_id, seed, init_style).to(device)
@@ -122,6 +131,12 @@ class Layer:
         self._batch = max_batch
         self._shadows_stale = False
         self.refresh_weights()
+
+    @property
+    def attn_causal(self) -> bool:
+        """False: this layer was asked for bidirectional attention (only a
+        BLOCK layer acts on it)."""
+        return self._attn_causal
 
     # -- compute ------------------------------------------------------------
     @property
