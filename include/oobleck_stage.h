@@ -83,10 +83,27 @@ typedef struct {
                            == 0, attn_pdrop == 0, attn_window 0 or >= seq_len,
                            and neither OB_BF16_FLASH=0 nor OB_FLASH_TR=0; else
                            the create fails */
+  int32_t n_kv_head;    /* BLOCK: K/V heads.  0 or n_head, what a zero-filled
+                           or keyword-built description gets: one K/V head per
+                           query head, today's layer in every launch and plan
+                           field.  0 < n_kv_head < n_head: grouped-query
+                           attention (1: multi-query), n_head / n_kv_head
+                           query heads share a K/V head
+                           (ob_flash_*_gqa_*bf16).  The qkv width becomes W =
+                           n_embd + 2 * 128 * n_kv_head wherever it was
+                           3 * n_embd: w_qkv [H, W], b_qkv [W], columns
+                           [Q | K heads | V heads].  Such a layer must be a
+                           flash layer: bf16, head_dim 128, n_head % n_kv_head
+                           == 0, seq_len % 128 == 0, attn_pdrop == 0, no band,
+                           not bidirectional, and none of OB_BF16_FLASH=0,
+                           OB_FLASH_TR=0, OB_FLASH_HD128=0; else the create
+                           fails */
 } ob_layer_desc;
 
 /* Number of fp32 elements in the layer's flat parameter buffer.  Layout is
- * the canonical order shared with oracle/gpt2_oracle.py::layer_param_spec. */
+ * the canonical order shared with oracle/gpt2_oracle.py::layer_param_spec; a
+ * BLOCK with 0 < n_kv_head < n_head has w_qkv [H, W] and b_qkv [W] (see
+ * n_kv_head). */
 int64_t ob_layer_param_count(const ob_layer_desc* desc);
 
 /* Create a layer; allocates the activation stash + workspace on the current
@@ -138,8 +155,8 @@ int ob_layer_create_ex(const ob_layer_desc* desc, const ob_dropout_desc* drop,
  * attn_pdrop == 0 and not OB_FLASH_TR=0; with OB_FLASH_BAND_DROP=1 (default
  * 0) and not OB_FLASH_DROP=0, attn_pdrop > 0 is also taken at head_dim 80 or
  * 96 and by a banded layer of any of the four head sizes; a layer with
- * attn_bidir set only under the conditions listed at that field), 0
- * otherwise.  Host-only. */
+ * attn_bidir set, and one with 0 < n_kv_head < n_head, only under the
+ * conditions listed at those fields), 0 otherwise.  Host-only. */
 int ob_layer_uses_flash(ob_layer_t l);
 /* The same decision for a description, before any layer exists: what
  * ob_layer_create_ex will take for `desc` with this attn_pdrop.  Host-only,
@@ -162,7 +179,9 @@ int ob_flash_eligible(const ob_layer_desc* desc, float attn_pdrop);
  * buffers (0 = not used; dp, dln, datt, dqkv, dy4, flash_bwd, flash_vt, dw_a,
  * dw_b, pd_fwd, pd_bwd, dm_attn, dm_mlp, det_main, det_side, det_fwd); the
  * layout of flash_bwd under OB_FLASH_TR=0: offsets of Q^T, K^T, dO^T (bf16
- * elements) and of D (floats).  Host-only, no GPU call. */
+ * elements) and of D (floats).  With 0 < n_kv_head < n_head the qkv region,
+ * the qkv shadows, dqkv and det_side are sized by W, and flash_bwd holds D
+ * followed by the dK/dV split slab.  Host-only, no GPU call. */
 int ob_layer_plan_query(const ob_layer_desc* desc,
                         const ob_dropout_desc* drop, int modes, int64_t* out,
                         int cap);
@@ -586,6 +605,36 @@ int ob_flash_bwd_bidir_d_bf16(const void* qkv, const void* O, const void* dO,
                               const void* lse, void* D_ws, void* dqkv,
                               void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
                               int64_t nh, float scale, void* stream);
+/* Grouped-query / multi-query causal flash attention (ob_flash_gqa_bf16.hip,
+ * DESIGN.md item 25): n_kv K/V heads serve nh query heads, G = nh / n_kv per
+ * group.  bf16, head_dim 128 only (H == 128 * nh), Sq % 128 == 0, 1 <= n_kv
+ * <= nh, nh % n_kv == 0, positive sizes.  qkv and dqkv are [B, Sq, W] with W =
+ * H + 2 * 128 * n_kv: query head h at columns 128*h, K head g at H + 128*g, V
+ * head g at H + 128*n_kv + 128*g; O, dO [B, Sq, H]; lse, D_ws [B*nh, Sq];
+ * dbias_qkv fp32 [W] (accumulated into) or null.  n_kv == nh calls the dense
+ * entry (bit-identical to it).  The backward runs dq (forming D into D_ws),
+ * then dkdv, whose blocks sum a K/V tile's gradient over the group's heads in
+ * registers.  split cuts the G heads of a group into that many parts, each
+ * with fp32 partials in its own slab [split][B*Sq][2*128*n_kv] (slab, a
+ * device buffer of slab_floats floats), folded in ascending order and rounded
+ * once; no atomic touches dK/dV, and the result is a pure function of the
+ * inputs and split.  split 0: ob_flash_gqa_split decides, lowered to what the
+ * slab holds (no slab: 1); split >= 1 forces that value, which must divide G
+ * and, above 1, needs slab_floats >= split * B*Sq * 2*128*n_kv.  Anything
+ * else returns 1 with the error set and launches nothing. */
+int ob_flash_fwd_gqa_bf16(const void* qkv, void* O, void* lse, int64_t B,
+                          int64_t Sq, int64_t H, int64_t nh, int64_t n_kv,
+                          float scale, void* stream);
+int ob_flash_bwd_gqa_d_bf16(const void* qkv, const void* O, const void* dO,
+                            const void* lse, void* D_ws, void* dqkv,
+                            void* dbias_qkv, int64_t B, int64_t Sq, int64_t H,
+                            int64_t nh, int64_t n_kv, int64_t split,
+                            void* slab, int64_t slab_floats, float scale,
+                            void* stream);
+/* The split ob_flash_bwd_gqa_d_bf16 takes for split == 0 on a device of `cus`
+ * compute units: a divisor of nh / n_kv.  Host-only, no GPU call. */
+int ob_flash_gqa_split(int64_t B, int64_t Sq, int64_t nh, int64_t n_kv,
+                       int64_t cus);
 /* Host-only queries of the block -> work mapping of the three causal kernels
  * (no GPU call).  kind: 0 forward, 1 dq, 2 dkdv.
  * rows: unit = wave 0..3 (forward, dq) or wave pair 0..1 (dkdv) of `block`

@@ -26,6 +26,7 @@ class ObLayerDesc(ctypes.Structure):
         ("dtype", ctypes.c_int32),
         ("attn_window", ctypes.c_int32),  # 0 = dense (the default)
         ("attn_bidir", ctypes.c_int32),  # 0 = causal (the default)
+        ("n_kv_head", ctypes.c_int32),  # 0 = n_head K/V heads (the default)
     ]
 
 
@@ -200,6 +201,12 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.ob_flash_fwd_bidir_bf16.argtypes = lib.ob_flash_fwd_nt_bf16.argtypes
     lib.ob_flash_bwd_bidir_d_bf16.argtypes = (
         lib.ob_flash_bwd_nt_d_bf16.argtypes)
+    # grouped-query: `n_kv` follows nh; the backward then takes (split, slab,
+    # slab_floats) before scale
+    lib.ob_flash_fwd_gqa_bf16.argtypes = lib.ob_flash_fwd_win_bf16.argtypes
+    lib.ob_flash_bwd_gqa_d_bf16.argtypes = (
+        lib.ob_flash_bwd_win_d_bf16.argtypes[:-2] + [i64, vp, i64, f32, vp])
+    lib.ob_flash_gqa_split.argtypes = [i64, i64, i64, i64, i64]
     # (seed, layer_id, tick, p): the site is always DROP_ATTN
     lib.ob_flash_fwd_nt_drop_bf16.argtypes = [vp, vp, vp, i64, i64, i64, i64,
                                               f32, u64, i32, u64, f32, vp]

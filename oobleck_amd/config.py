@@ -32,6 +32,19 @@ class ModelConfig:
     # attention of an encoder (Megatron-BERT, ViT).  bf16 flash layers at
     # head_dim 64 with attn_pdrop == 0 and no window only.
     attn_causal: bool = True
+    # K/V heads of every block.  0 (or n_head): one per query head.  0 <
+    # n_kv_head < n_head: grouped-query attention (1: multi-query, GPT-BigCode),
+    # n_head / n_kv_head query heads share a K/V head and the packed qkv width
+    # is qkv_width.  bf16 flash layers at head_dim 128 with attn_pdrop == 0,
+    # dense and causal, only.
+    n_kv_head: int = 0
+
+    @property
+    def qkv_width(self) -> int:
+        """Columns of w_qkv / b_qkv: [Q (n_embd) | K heads | V heads]."""
+        if self.n_kv_head in (0, self.n_head):
+            return 3 * self.n_embd
+        return self.n_embd + 2 * 128 * self.n_kv_head
 
     @property
     def n_layers_total(self) -> int:
@@ -67,6 +80,13 @@ GPT3_6_7B = ModelConfig(n_embd=4096, n_head=32, n_layer=32, n_positions=2048)
 # head_dim 96 and 80: flash layers only with OB_FLASH_HD96=1
 GPT3_760M = ModelConfig(n_embd=1536, n_head=16, n_layer=24, n_positions=2048)
 GPT3_2_7B = ModelConfig(n_embd=2560, n_head=32, n_layer=32, n_positions=2048)
+# GPT-BigCode's SantaCoder (Allal et al. 2023): the GPT-2 block with
+# multi-query attention, 16 query heads on one K/V head of 128 columns
+SANTACODER = ModelConfig(n_embd=2048, n_head=16, n_layer=24, n_positions=2048,
+                         vocab_size=49280, n_kv_head=1)
+# a grouped-query example: the 6.7B block with 8 K/V heads (groups of 4)
+GPT3_6_7B_GQA8 = ModelConfig(n_embd=4096, n_head=32, n_layer=32,
+                             n_positions=2048, n_kv_head=8)
 
 
 @dataclass

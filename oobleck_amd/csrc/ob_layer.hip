@@ -351,13 +351,14 @@ struct BlockParams {
   int64_t ln1_w, ln1_b, w_qkv, b_qkv, w_attnproj, b_attnproj, ln2_w, ln2_b,
       w_fc, b_fc, w_mlpproj, b_mlpproj, total;
 };
-static BlockParams block_params(int64_t H) {
+// Wq: the qkv width, 3H or a grouped-query layer's W (ob_plan_qkv_width)
+static BlockParams block_params(int64_t H, int64_t Wq) {
   BlockParams p;
   int64_t o = 0;
   p.ln1_w = o; o += H;
   p.ln1_b = o; o += H;
-  p.w_qkv = o; o += H * 3 * H;
-  p.b_qkv = o; o += 3 * H;
+  p.w_qkv = o; o += H * Wq;
+  p.b_qkv = o; o += Wq;
   p.w_attnproj = o; o += H * H;
   p.b_attnproj = o; o += H;
   p.ln2_w = o; o += H;
@@ -374,7 +375,8 @@ extern "C" int64_t ob_layer_param_count(const ob_layer_desc* d) {
   const int64_t H = d->n_embd, V = d->vocab_size, P = d->n_positions;
   switch (d->kind) {
     case OB_KIND_EMBED: return V * H + P * H;
-    case OB_KIND_BLOCK: return block_params(H).total;
+    case OB_KIND_BLOCK:
+      return block_params(H, ob_plan_qkv_width(*d)).total;
     case OB_KIND_FINAL: return 2 * H + V * H;
   }
   return -1;
@@ -522,9 +524,10 @@ extern "C" int ob_layer_refresh_weights(ob_layer_t l, void* stream) {
     case OB_KIND_EMBED:
       return 0;  // embedding reads the fp32 master directly
     case OB_KIND_BLOCK: {
-      const BlockParams bp = block_params(H);
-      if (ob_f32_to_bf16(p + bp.w_qkv, shadow(l, SH_QKV), 3 * H * H, stream) ||
-          ob_f32_to_bf16_t_ld(p + bp.w_qkv, shadow(l, SH_QKV_T), H, 3 * H, H,
+      const int64_t Wq = ob_plan_qkv_width(l->d);
+      const BlockParams bp = block_params(H, Wq);
+      if (ob_f32_to_bf16(p + bp.w_qkv, shadow(l, SH_QKV), H * Wq, stream) ||
+          ob_f32_to_bf16_t_ld(p + bp.w_qkv, shadow(l, SH_QKV_T), H, Wq, H,
                               stream) ||
           ob_f32_to_bf16(p + bp.w_attnproj, shadow(l, SH_AP), H * H, stream) ||
           ob_f32_to_bf16_t_ld(p + bp.w_attnproj, shadow(l, SH_AP_T), H, H, H,
@@ -614,7 +617,7 @@ static int block_forward(ob_layer* l, int slot, const float* in, float* out,
   const int64_t hd = H / nh;
   const float* p = l->params;
   const BlockStash<float> s(l, slot);
-  const BlockParams bp = block_params(H);
+  const BlockParams bp = block_params(H, ob_plan_qkv_width(l->d));
   const bool dA = l->slot_drop[slot] && l->p_attn > 0.f;
   const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;
 
@@ -721,19 +724,21 @@ enum {
 enum { LG_LM = 0, LG_DLNOUT, LG_DW_LM, LG_FINAL_N };
 
 // res: the two projections fold their residual (false under residual dropout)
-static void block_gemms(int64_t H, int64_t BS, bool res, ob_lt_shape* g) {
-  g[LG_QKV] = ob_lt_linear(BS, H, 3 * H, true, false);
+// Wq: the qkv width (ob_plan_qkv_width)
+static void block_gemms(int64_t H, int64_t Wq, int64_t BS, bool res,
+                        ob_lt_shape* g) {
+  g[LG_QKV] = ob_lt_linear(BS, H, Wq, true, false);
   g[LG_AP] = ob_lt_linear(BS, H, H, true, res);
   g[LG_FC] = ob_lt_linear(BS, H, 4 * H, true, false);
   g[LG_MP] = ob_lt_linear(BS, 4 * H, H, true, res);
   g[LG_DX_MP] = ob_lt_linear(BS, H, 4 * H, false, false);
   g[LG_DX_FC] = ob_lt_linear(BS, 4 * H, H, false, false);
   g[LG_DX_AP] = ob_lt_linear(BS, H, H, false, false);
-  g[LG_DX_QKV] = ob_lt_linear(BS, 3 * H, H, false, false);
+  g[LG_DX_QKV] = ob_lt_linear(BS, Wq, H, false, false);
   g[LG_DW_MP] = ob_lt_dw(4 * H, H, BS, 4 * H);
   g[LG_DW_FC] = ob_lt_dw(H, 4 * H, BS, H);
   g[LG_DW_AP] = ob_lt_dw(H, H, BS, H);
-  g[LG_DW_QKV] = ob_lt_dw(H, 3 * H, BS, H);
+  g[LG_DW_QKV] = ob_lt_dw(H, Wq, BS, H);
 }
 
 // lm_head N = v_pad, d_lnout K = v_pad, dW_lm M = V over v_pad-wide rows
@@ -765,7 +770,7 @@ static void ob_layer_lt_list(const ob_layer_desc* d, bool resid_drop,
   ob_lt_shape g[LG_BLOCK_N];
   int n = 0;
   if (d->kind == OB_KIND_BLOCK) {
-    block_gemms(H, BS, true, g);
+    block_gemms(H, ob_plan_qkv_width(*d), BS, true, g);
     n = LG_BLOCK_N;
   } else if (d->kind == OB_KIND_FINAL) {
     final_gemms(H, V, ob_v_pad(V), BS, g);
@@ -774,7 +779,7 @@ static void ob_layer_lt_list(const ob_layer_desc* d, bool resid_drop,
   for (int i = 0; i < n; i++)
     if (lt_routed(g[i])) out->push_back(g[i]);
   if (d->kind == OB_KIND_BLOCK && resid_drop) {
-    block_gemms(H, BS, false, g);
+    block_gemms(H, ob_plan_qkv_width(*d), BS, false, g);
     for (int i : {LG_AP, LG_MP})
       if (lt_routed(g[i])) out->push_back(g[i]);
   }
@@ -863,11 +868,11 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   const int64_t hd = H / nh;
   const float* p = l->params;
   const BlockStash<__bf16> s(l, slot);
-  const BlockParams bp = block_params(H);
+  const BlockParams bp = block_params(H, ob_plan_qkv_width(l->d));
   const bool dA = l->slot_drop[slot] && l->p_attn > 0.f;
   const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;
   ob_lt_shape lg[LG_BLOCK_N];
-  block_gemms(H, BS, !dR, lg);
+  block_gemms(H, ob_plan_qkv_width(l->d), BS, !dR, lg);
 
   // ln1 reads the input once and also writes its stash copy x
   if (OB_PROF(OB_PF_LN, stream,
@@ -882,7 +887,15 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   if (l->plan.flash && flash_tr()) {
     // the fused kernel writes O and the per-row LSE (stored where the
     // materialized-P path keeps P)
-    if (ob_plan_bidir(l->d)) {
+    if (ob_plan_gqa(l->d)) {
+      // grouped-query layer (the plan admits it at head_dim 128, dense and
+      // causal, with attn_pdrop == 0 only)
+      if (OB_PROF(OB_PF_FLASH_FWD, stream,
+                  ob_flash_fwd_gqa_bf16(s.qkv, s.am, s.lseP, B, Sq, H, nh,
+                                        l->d.n_kv_head,
+                                        1.f / sqrtf((float)hd), stream)))
+        return 1;
+    } else if (ob_plan_bidir(l->d)) {
       // bidirectional layer (the plan admits it at head_dim 64 with
       // attn_pdrop == 0 and no band only)
       if (OB_PROF(OB_PF_FLASH_FWD, stream,
@@ -1037,12 +1050,12 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   const BlockStash<__bf16> s(l, slot);
   const BwdWs<__bf16> w(l);
   float* g = l->grads;
-  const BlockParams bp = block_params(H);
+  const BlockParams bp = block_params(H, ob_plan_qkv_width(l->d));
   // the masks this slot's forward drew, regenerated from its tick
   const bool dA = l->slot_drop[slot] && l->p_attn > 0.f;
   const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;
   ob_lt_shape lg[LG_BLOCK_N];
-  block_gemms(H, BS, !dR, lg);
+  block_gemms(H, ob_plan_qkv_width(l->d), BS, !dR, lg);
   // deterministic mode: the same calls, same places, same streams, with
   // the stream's slab (null: the atomic kernels)
   const bool det = ob_deterministic() != 0;
@@ -1131,7 +1144,17 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     // also adds the b_qkv grad (column sums of DQKV) from its accumulators
     // (deterministic mode: not asked for; the side-stream colsum below)
     float* const dbq = det ? nullptr : g + bp.b_qkv;
-    if (ob_plan_bidir(l->d)) {
+    if (ob_plan_gqa(l->d)) {
+      // the split slab follows D (sized for the layer's max_batch) in
+      // WS_FLASH_BWD; split 0: the rule, a fixed-order fold either way
+      const int64_t d_floats = (int64_t)l->d.max_batch * nh * Sq;
+      if (OB_PROF(OB_PF_FLASH_BWD, stream,
+                  ob_flash_bwd_gqa_d_bf16(
+                      s.qkv, s.am, w.DATT, s.lseP, w.D, w.DQKV, dbq, B, Sq, H,
+                      nh, l->d.n_kv_head, 0, w.D + d_floats,
+                      l->plan.ws[WS_FLASH_BWD] - d_floats, scale, stream)))
+        return 1;
+    } else if (ob_plan_bidir(l->d)) {
       if (OB_PROF(OB_PF_FLASH_BWD, stream,
                   ob_flash_bwd_bidir_d_bf16(s.qkv, s.am, w.DATT, s.lseP, w.D,
                                             w.DQKV, dbq, B, Sq, H, nh, scale,
@@ -1234,7 +1257,8 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
   OB_SIDE_FENCE(S(stream), g_side.stream);  // DQKV ready
   if ((!flash_nt || det) &&
       OB_PROF(OB_PF_ELEM, side,
-              ob_colsum_ws(w.DQKV, g + bp.b_qkv, BS, 3 * H,
+              ob_colsum_ws(w.DQKV, g + bp.b_qkv, BS,
+                           ob_plan_qkv_width(l->d),
                            det ? ws<float>(WS_DET_SIDE) : nullptr, side)))
     return 1;
   if (OB_PROF(OB_PF_GEMM_DW, side,
@@ -1380,7 +1404,7 @@ static int block_backward(ob_layer* l, int slot, const float* dout, float* din,
   const BlockStash<float> s(l, slot);
   const BwdWs<float> w(l);
   float* g = l->grads;
-  const BlockParams bp = block_params(H);
+  const BlockParams bp = block_params(H, ob_plan_qkv_width(l->d));
   // the masks this slot's forward drew, regenerated from its tick
   const bool dA = l->slot_drop[slot] && l->p_attn > 0.f;
   const bool dR = l->slot_drop[slot] && l->p_resid > 0.f;

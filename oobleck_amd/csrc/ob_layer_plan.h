@@ -36,8 +36,10 @@ enum {
   WS_DLN,        // main: grad of a LayerNorm's output [BS, H]
   WS_DATT,       // main: grad of the attention output [BS, H]
   WS_DQKV,       // main, read by side until the join: grad of qkv [BS, 3H]
+                 // (a grouped-query layer: [BS, W], ob_plan_qkv_width)
   WS_DY4,        // main, read by side until the join: MLP grads [BS, 4H]
-  WS_FLASH_BWD,  // main: flash D [B*nh, S]; OB_FLASH_TR=0: Q^T|K^T|dO^T|D
+  WS_FLASH_BWD,  // main: flash D [B*nh, S]; OB_FLASH_TR=0: Q^T|K^T|dO^T|D;
+                 // a grouped-query layer: D, then the dK/dV split slab
   WS_FLASH_VT,   // fwd: V^T, OB_FLASH_TR=0 only
   WS_DW_A,       // side: BLOCK: the fp32 slab [s, M, N] of a sliced dW call
                  // (ob_dw_slices.h), or, when the library takes no part, the
@@ -102,6 +104,29 @@ inline int64_t ob_v_pad(int64_t V) { return (V + 255) / 256 * 256; }
 // layer at head_dim 64 only, with attn_pdrop == 0, no band and flash_tr: those
 // kernels are production-only and have neither dropout nor banded variants.
 // Its plan is the causal flash plan of the same description.
+// A grouped-query layer (ob_plan_gqa: 0 < n_kv_head < n_head;
+// ob_flash_gqa_bf16.hip) is a flash layer at head_dim 128 only, with n_head %
+// n_kv_head == 0, attn_pdrop == 0, no band, causal, flash_tr and flash_hd128:
+// no other route knows its qkv layout.  Its qkv width is W = H + 2 * 128 *
+// n_kv_head (ob_plan_qkv_width) wherever the plan below says 3H, and
+// WS_FLASH_BWD holds D followed by the dK/dV split slab, sized for the
+// largest split ob_flash_gqa_split can return for the description on any CU
+// count.  n_kv_head 0 or n_head is today's layer in every field.
+inline bool ob_plan_gqa(const ob_layer_desc& d) {
+  return d.kind == OB_KIND_BLOCK && d.n_kv_head != 0 &&
+         d.n_kv_head != d.n_head;
+}
+inline int64_t ob_plan_qkv_width(const ob_layer_desc& d) {
+  return ob_plan_gqa(d) ? d.n_embd + 2 * 128 * (int64_t)d.n_kv_head
+                        : 3 * (int64_t)d.n_embd;
+}
+// floats of the split slab behind D in WS_FLASH_BWD
+inline int64_t ob_plan_gqa_slab(const ob_layer_desc& d) {
+  if (!ob_plan_gqa(d)) return 0;
+  const int64_t s = ob_flash_gqa_split(d.max_batch, d.seq_len, d.n_head,
+                                       d.n_kv_head, INT32_MAX);
+  return s > 1 ? s * d.max_batch * d.seq_len * 2 * 128 * d.n_kv_head : 0;
+}
 inline bool ob_plan_windowed(const ob_layer_desc& d) {
   return d.kind == OB_KIND_BLOCK && d.attn_window > 0 &&
          d.attn_window < d.seq_len;
@@ -111,6 +136,11 @@ inline bool ob_plan_bidir(const ob_layer_desc& d) {
 }
 inline bool ob_plan_flash(const ob_layer_desc& d, float p_attn,
                           const ob_layer_modes& m) {
+  if (ob_plan_gqa(d) &&
+      !(p_attn == 0.f && !ob_plan_windowed(d) && d.attn_window >= 0 &&
+        !ob_plan_bidir(d) && d.n_kv_head > 0 && d.n_head > 0 &&
+        d.n_head % d.n_kv_head == 0 && d.n_embd == 128 * d.n_head))
+    return false;  // head_dim 128 then asks for flash_tr and flash_hd128
   if (ob_plan_bidir(d) &&
       !(p_attn == 0.f && m.flash_tr && !ob_plan_windowed(d) &&
         d.attn_window >= 0 && d.n_head > 0 && d.n_embd == 64 * d.n_head))
@@ -137,6 +167,7 @@ inline ob_layer_plan ob_layer_plan_of(const ob_layer_desc& d, float p_resid,
   const int64_t Bm = d.max_batch, Sq = d.seq_len, H = d.n_embd, nh = d.n_head,
                 V = d.vocab_size;
   const int64_t BS = Bm * Sq, BSH = BS * H, PSS = Bm * nh * Sq * Sq;
+  const int64_t Wq = ob_plan_qkv_width(d);  // 3H, or a grouped-query W
   const int64_t half4 = (4 * H * BS + 1) / 2;  // [BS, 4H] bf16, in floats
   const bool bf16 = d.dtype == 1;
   p.v_pad = ob_v_pad(V);
@@ -156,6 +187,12 @@ inline ob_layer_plan ob_layer_plan_of(const ob_layer_desc& d, float p_resid,
       // the materialized-P route has no band
       if (d.attn_window < 0)
         p.error = "attn_window must be >= 0";
+      else if (ob_plan_gqa(d) && !p.flash)
+        p.error =
+            "0 < n_kv_head < n_head needs a flash layer: bf16, head_dim 128, "
+            "n_head % n_kv_head == 0, seq_len % 128 == 0, attn_pdrop == 0, "
+            "attn_window 0 or >= seq_len, attn_bidir == 0, and none of "
+            "OB_BF16_FLASH=0, OB_FLASH_TR=0, OB_FLASH_HD128=0";
       else if (ob_plan_bidir(d) && !p.flash)
         p.error =
             "attn_bidir needs a flash layer: bf16, head_dim 64, seq_len % 128 "
@@ -169,22 +206,22 @@ inline ob_layer_plan ob_layer_plan_of(const ob_layer_desc& d, float p_resid,
             "OB_FLASH_DROP=0), and none of OB_BF16_FLASH=0, OB_FLASH_TR=0, "
             "OB_FLASH_HD128=0 (head_dim 128)";
       st(ST_X, BSH), st(ST_MEAN1, BS), st(ST_RSTD1, BS), st(ST_LN1, BSH);
-      st(ST_QKV, 3 * BSH), st(ST_P, p.flash ? Bm * nh * Sq : PSS);
+      st(ST_QKV, BS * Wq), st(ST_P, p.flash ? Bm * nh * Sq : PSS);
       st(ST_ATTNM, BSH), st(ST_HMID, BSH), st(ST_MEAN2, BS), st(ST_RSTD2, BS);
       st(ST_LN2, BSH), st(ST_U, 4 * BSH), st(ST_G, 4 * BSH);
       p.ws[WS_DP] = p.flash ? 0 : PSS;
       p.ws[WS_DLN] = p.ws[WS_DATT] = BSH;
-      p.ws[WS_DQKV] = 3 * BSH, p.ws[WS_DY4] = 4 * BSH;
+      p.ws[WS_DQKV] = BS * Wq, p.ws[WS_DY4] = 4 * BSH;
       if (p_attn > 0.f && !p.flash) p.ws[WS_PD_FWD] = p.ws[WS_PD_BWD] = PSS;
       if (p_resid > 0.f) p.ws[WS_DM_ATTN] = p.ws[WS_DM_MLP] = BSH;
       if (!bf16) break;
-      sh(SH_QKV, 3 * H * H), sh(SH_QKV_T, 3 * H * H), sh(SH_AP, H * H);
+      sh(SH_QKV, H * Wq), sh(SH_QKV_T, H * Wq), sh(SH_AP, H * H);
       sh(SH_AP_T, H * H), sh(SH_FC, 4 * H * H), sh(SH_FC_T, 4 * H * H);
       sh(SH_MP, 4 * H * H), sh(SH_MP_T, 4 * H * H);
       p.side = true;
       p.ws[WS_DW_A] = p.ws[WS_DW_B] = half4;
       if (p.flash && m.flash_tr) {
-        p.ws[WS_FLASH_BWD] = Bm * nh * Sq;
+        p.ws[WS_FLASH_BWD] = Bm * nh * Sq + ob_plan_gqa_slab(d);
       } else if (p.flash) {
         p.ws[WS_FLASH_BWD] = p.ws[WS_FLASH_VT] = half4;
         p.pk_kt = BSH, p.pk_dot = 2 * BSH, p.pk_d = (3 * BSH + 1) / 2;
@@ -195,7 +232,7 @@ inline ob_layer_plan ob_layer_plan_of(const ob_layer_desc& d, float p_resid,
       p.ws[WS_DET_MAIN] =
           max2(max2(det(OB_DET_WS_GELU, 4 * H), det(OB_DET_WS_LN, H)),
                p_resid > 0.f ? det(OB_DET_WS_DROP_CS, H) : 0);
-      p.ws[WS_DET_SIDE] = det(OB_DET_WS_COLSUM, 3 * H);
+      p.ws[WS_DET_SIDE] = det(OB_DET_WS_COLSUM, Wq);
       break;
     case OB_KIND_FINAL:
       st(ST_X, BSH), st(ST_MEAN1, BS), st(ST_RSTD1, BS), st(ST_LN1, BSH);

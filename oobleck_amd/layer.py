@@ -83,10 +83,12 @@ class Layer:
             n_positions=cfg.n_positions, vocab_size=cfg.vocab_size,
             max_batch=max_batch, seq_len=seq_len, n_slots=n_slots,
             dtype=0 if dtype == "f32" else 1, attn_window=self.attn_window,
-            attn_bidir=0 if self._attn_causal else 1)
+            attn_bidir=0 if self._attn_causal else 1,
+            n_kv_head=cfg.n_kv_head)
         n = ext.ob_layer_param_count(ctypes.byref(self._desc))
         assert n > 0
         init = init_layer_params(cfg, layer_id, seed, init_style).to(device)
+        assert init.numel() == n  # params.layer_param_spec's layout
         group_size = 1
         if process_group is not None and torch.distributed.is_initialized():
             group_size = torch.distributed.get_world_size(process_group)
@@ -137,6 +139,14 @@ class Layer:
         """False: this layer was asked for bidirectional attention (only a
         BLOCK layer acts on it)."""
         return self._attn_causal
+
+    @property
+    def n_kv_head(self) -> int:
+        """K/V heads this layer was asked for (cfg.n_kv_head; 0 = n_head;
+        only a BLOCK layer acts on it).  0 < n_kv_head < n_head is grouped-
+        query attention: a bf16 flash layer at head_dim 128 with attn_pdrop
+        == 0, dense and causal, or the create fails."""
+        return int(self._desc.n_kv_head)
 
     # -- compute ------------------------------------------------------------
     @property

@@ -27,9 +27,10 @@ def layer_param_spec(cfg: ModelConfig, kind: int) -> list[tuple[str, tuple[int, 
     if kind == KIND_EMBED:
         return [("wte", (V, H)), ("wpe", (P, H))]
     if kind == KIND_BLOCK:
+        W = cfg.qkv_width  # 3H; grouped-query: H + 2 * 128 * n_kv_head
         return [
             ("ln1_w", (H,)), ("ln1_b", (H,)),
-            ("w_qkv", (H, 3 * H)), ("b_qkv", (3 * H,)),
+            ("w_qkv", (H, W)), ("b_qkv", (W,)),
             ("w_attnproj", (H, H)), ("b_attnproj", (H,)),
             ("ln2_w", (H,)), ("ln2_b", (H,)),
             ("w_fc", (H, 4 * H)), ("b_fc", (4 * H,)),

@@ -39,6 +39,15 @@
 # kernels (ob_flash_*_win_drop_bf16 / ob_flash_*_hd96_drop_bf16) against the
 # plain ones at the same window: the A/B above with the arms "plain" and
 # "drop", and drop / plain of the minima.
+#
+# --n-kv N (with --head-dim 128, N a proper divisor of nh) times the
+# grouped-query entries (ob_flash_fwd_gqa_bf16 / ob_flash_bwd_gqa_d_bf16, N
+# K/V heads) against the dense head_dim 128 ones at the same --shape: the
+# forward, and the backward at every split that divides nh / N.  The arms
+# alternate in one process, --repeats rounds of 30 back-to-back calls between
+# device events; it prints every round, each arm's median and max - min, and
+# the TF of the median.  The backward rows differ only in their dkdv (and
+# fold) launches: the dq kernel is the same in every gqa row.
 import argparse
 import ctypes
 import pathlib
@@ -56,6 +65,8 @@ ap.add_argument("--head-dim", type=int, default=64, choices=(64, 80, 96, 128))
 ap.add_argument("--shape", default="8,12,1024", metavar="B,nh,S")
 ap.add_argument("--window", type=int, default=0, metavar="W",
                 help="time the banded entries against the dense ones")
+ap.add_argument("--n-kv", type=int, default=0, metavar="N",
+                help="time the grouped-query entries against the dense ones")
 ap.add_argument("--repeats", type=int, default=7)
 args = ap.parse_args()
 
@@ -205,6 +216,59 @@ def timeit_once(fn, reps=30):
     torch.cuda.synchronize()
     return st.elapsed_time(en) / reps * 1e3
 
+
+if args.n_kv:
+    n_kv = args.n_kv
+    assert hd == 128 and 0 < n_kv < nh and nh % n_kv == 0, \
+        "--n-kv needs --head-dim 128 and a proper divisor of nh"
+    G, Hkv = nh // n_kv, 128 * n_kv
+    qkv_g = (torch.randn(B, S, H + 2 * Hkv, generator=g) * 0.3) \
+        .to(DEV).bfloat16()
+    dqkv_g = torch.zeros_like(qkv_g)
+    dbias_g = torch.zeros(H + 2 * Hkv, device=DEV)
+    O_g, lse_g, D_g = torch.empty_like(O), torch.empty_like(lse), \
+        torch.empty_like(D)
+    slab = torch.empty(G * B * S * 2 * Hkv, device=DEV)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    rule = ext.ob_flash_gqa_split(B, S, nh, n_kv, cus)
+
+    def fwd_gqa():
+        check(ext.ob_flash_fwd_gqa_bf16(ptr(qkv_g), ptr(O_g), ptr(lse_g), B,
+                                        S, H, nh, n_kv, scale, stream()))
+
+    def bwd_gqa(split):
+        return lambda: check(ext.ob_flash_bwd_gqa_d_bf16(
+            ptr(qkv_g), ptr(O_g), ptr(dO), ptr(lse_g), ptr(D_g), ptr(dqkv_g),
+            ptr(dbias_g), B, S, H, nh, n_kv, split, ptr(slab), slab.numel(),
+            scale, stream()))
+
+    splits = [s for s in range(1, G + 1) if G % s == 0]
+    print(f"head_dim 128, (B, nh, n_kv, S) = ({B}, {nh}, {n_kv}, {S}), "
+          f"{cus} CUs: dkdv blocks at split 1 = {B * n_kv * (S // 64)}, "
+          f"ob_flash_gqa_split = {rule}")
+    fwd_new()
+    fwd_gqa()  # each backward reads the O and lse of its own arm's forward
+    unit = B * nh * S * S * hd * 1e-6  # MFLOP per causal GEMM pair / 2
+    for title, gemms, arms in (
+            ("fwd", 2, [("mha", fwd_new), ("gqa", fwd_gqa)]),
+            ("bwd (dq + dkdv [+ fold], D in-kernel, + bias)", 5,
+             [("mha", lambda: bwd_new_d(dbias))] +
+             [(f"gqa split {s}", bwd_gqa(s)) for s in splits])):
+        for _, fn in arms:
+            for _ in range(5):
+                fn()
+        torch.cuda.synchronize()
+        us = [[] for _ in arms]
+        for _ in range(args.repeats):  # the arms alternate
+            for a, (_, fn) in enumerate(arms):
+                us[a].append(timeit_once(fn))
+        print(title)
+        for (name, _), v in zip(arms, us):
+            med = sorted(v)[len(v) // 2]
+            print(f"  {name:12s} us: " + " ".join(f"{x:7.1f}" for x in v) +
+                  f" | median {med:.1f} spread {max(v) - min(v):.1f}; "
+                  f"{gemms * unit / med:.1f} TF")
+    sys.exit(0)
 
 if args.attn_pdrop > 0.0 and (args.window or hd in (80, 96)):
     W = args.window
