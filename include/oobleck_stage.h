@@ -98,6 +98,20 @@ typedef struct {
                            not bidirectional, and none of OB_BF16_FLASH=0,
                            OB_FLASH_TR=0, OB_FLASH_HD128=0; else the create
                            fails */
+  int32_t attn_segments; /* BLOCK: 0 = a row of seq_len tokens is one
+                           document, what a zero-filled or keyword-built
+                           description gets: today's layer in every launch
+                           and plan field.  Nonzero: document-masked causal
+                           attention for packed sequences
+                           (ob_flash_*_seg_*bf16): the layer keeps the bounds
+                           (lo, hi) of every slot, set by
+                           ob_layer_set_doc_starts, and query i sees the keys
+                           of its own document up to i.  Such a layer must be
+                           a flash layer: bf16, head_dim 64 or 128, seq_len %
+                           128 == 0, attn_pdrop == 0, no band, causal,
+                           n_kv_head 0 or n_head, and none of OB_BF16_FLASH=0,
+                           OB_FLASH_TR=0, OB_FLASH_HD128=0 (head_dim 128);
+                           else the create fails */
 } ob_layer_desc;
 
 /* Number of fp32 elements in the layer's flat parameter buffer.  Layout is
@@ -155,8 +169,9 @@ int ob_layer_create_ex(const ob_layer_desc* desc, const ob_dropout_desc* drop,
  * attn_pdrop == 0 and not OB_FLASH_TR=0; with OB_FLASH_BAND_DROP=1 (default
  * 0) and not OB_FLASH_DROP=0, attn_pdrop > 0 is also taken at head_dim 80 or
  * 96 and by a banded layer of any of the four head sizes; a layer with
- * attn_bidir set, and one with 0 < n_kv_head < n_head, only under the
- * conditions listed at those fields), 0 otherwise.  Host-only. */
+ * attn_bidir set, one with 0 < n_kv_head < n_head, and one with
+ * attn_segments set, only under the conditions listed at those fields), 0
+ * otherwise.  Host-only. */
 int ob_layer_uses_flash(ob_layer_t l);
 /* The same decision for a description, before any layer exists: what
  * ob_layer_create_ex will take for `desc` with this attn_pdrop.  Host-only,
@@ -181,7 +196,9 @@ int ob_flash_eligible(const ob_layer_desc* desc, float attn_pdrop);
  * layout of flash_bwd under OB_FLASH_TR=0: offsets of Q^T, K^T, dO^T (bf16
  * elements) and of D (floats).  With 0 < n_kv_head < n_head the qkv region,
  * the qkv shadows, dqkv and det_side are sized by W, and flash_bwd holds D
- * followed by the dK/dV split slab.  Host-only, no GPU call. */
+ * followed by the dK/dV split slab.  A BLOCK with attn_segments set reports
+ * ids_count = max_batch * seq_len * n_slots: one int64 per token and slot is
+ * the two int32 bounds (lo, hi) of that token.  Host-only, no GPU call. */
 int ob_layer_plan_query(const ob_layer_desc* desc,
                         const ob_dropout_desc* drop, int modes, int64_t* out,
                         int cap);
@@ -194,6 +211,17 @@ int ob_layer_set_training(ob_layer_t l, int on);
  * with dropout then post-increments it.  The tick a forward used is kept per
  * slot, and the backward of slot s uses slot s's tick. */
 int ob_layer_set_dropout_tick(ob_layer_t l, uint64_t tick);
+
+/* A layer with attn_segments: set the documents of the microbatch in stash
+ * slot `slot`, for the current batch (ob_layer_set_batch).  doc_start is
+ * device int32 [B, S], nonzero where a token begins a document (position 0
+ * always does); ob_flash_seg_bounds_i32 turns it into the slot's bounds,
+ * asynchronously on `stream`.  NULL resets the slot to one document per row,
+ * which is how the create leaves every slot.  A slot's bounds persist until
+ * the next call; the forward and the backward of the slot use them.  Fails on
+ * a layer without attn_segments. */
+int ob_layer_set_doc_starts(ob_layer_t l, int32_t slot, const void* doc_start,
+                            void* stream);
 
 /* Bind caller-owned device fp32 buffers of ob_layer_param_count() elements:
  * params (read/write: forward reads, adam writes) and grads (backward
@@ -631,6 +659,33 @@ int ob_flash_bwd_gqa_d_bf16(const void* qkv, const void* O, const void* dO,
                             int64_t nh, int64_t n_kv, int64_t split,
                             void* slab, int64_t slab_floats, float scale,
                             void* stream);
+/* Document-masked (block-diagonal) causal flash attention for packed
+ * sequences (ob_flash_seg_bf16.hip): query row i of batch
+ * row b attends the keys j with lo[b,i] <= j <= i.  lo and hi are device int32
+ * [B, Sq]: lo[b,i] the first token of i's document, hi[b,j] the last token of
+ * j's; both non-decreasing along a row, lo[i] <= i <= hi[i], constant within
+ * a document.  ob_flash_seg_bounds_i32 writes them from doc_start, device
+ * int32 [B, Sq] or null, nonzero where a token begins a document; position 0
+ * always does, null means no other start, and every input yields valid
+ * bounds (B, Sq > 0; Sq need not be a multiple of 128).  The kernels clamp
+ * what they load (lo to [0, i], hi to [j, Sq-1]), so no array content sends
+ * them outside their buffers; bounds that break the rules above give
+ * undefined values, not faults.  The two attention entries: the shape rules,
+ * buffers, LSE, D_ws and dbias_qkv contracts of ob_flash_fwd_win_bf16 /
+ * ob_flash_bwd_win_d_bf16 (head_dim 64 or 128, Sq % 128 == 0, positive sizes;
+ * dq forms D into D_ws, then dkdv; a null dbias_qkv skips the bias sum).
+ * Anything else returns 1 with the error set and launches nothing.  Work
+ * grows with the sum of the squared document lengths.  No dropout. */
+int ob_flash_seg_bounds_i32(const void* doc_start, void* lo, void* hi,
+                            int64_t B, int64_t Sq, void* stream);
+int ob_flash_fwd_seg_bf16(const void* qkv, const void* lo, void* O, void* lse,
+                          int64_t B, int64_t Sq, int64_t H, int64_t nh,
+                          float scale, void* stream);
+int ob_flash_bwd_seg_d_bf16(const void* qkv, const void* O, const void* dO,
+                            const void* lse, const void* lo, const void* hi,
+                            void* D_ws, void* dqkv, void* dbias_qkv,
+                            int64_t B, int64_t Sq, int64_t H, int64_t nh,
+                            float scale, void* stream);
 /* The split ob_flash_bwd_gqa_d_bf16 takes for split == 0 on a device of `cus`
  * compute units: a divisor of nh / n_kv.  Host-only, no GPU call. */
 int ob_flash_gqa_split(int64_t B, int64_t Sq, int64_t nh, int64_t n_kv,

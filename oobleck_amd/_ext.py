@@ -27,6 +27,7 @@ class ObLayerDesc(ctypes.Structure):
         ("attn_window", ctypes.c_int32),  # 0 = dense (the default)
         ("attn_bidir", ctypes.c_int32),  # 0 = causal (the default)
         ("n_kv_head", ctypes.c_int32),  # 0 = n_head K/V heads (the default)
+        ("attn_segments", ctypes.c_int32),  # 0 = one document per row
     ]
 
 
@@ -207,6 +208,13 @@ def _configure(lib: ctypes.CDLL) -> ctypes.CDLL:
     lib.ob_flash_bwd_gqa_d_bf16.argtypes = (
         lib.ob_flash_bwd_win_d_bf16.argtypes[:-2] + [i64, vp, i64, f32, vp])
     lib.ob_flash_gqa_split.argtypes = [i64, i64, i64, i64, i64]
+    # document-masked: the bounds `lo` (and `hi`) follow qkv (lse)
+    lib.ob_flash_seg_bounds_i32.argtypes = [vp, vp, vp, i64, i64, vp]
+    lib.ob_flash_fwd_seg_bf16.argtypes = [vp, vp, vp, vp, i64, i64, i64, i64,
+                                          f32, vp]
+    lib.ob_flash_bwd_seg_d_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp,
+                                            vp, i64, i64, i64, i64, f32, vp]
+    lib.ob_layer_set_doc_starts.argtypes = [vp, i32, vp, vp]
     # (seed, layer_id, tick, p): the site is always DROP_ATTN
     lib.ob_flash_fwd_nt_drop_bf16.argtypes = [vp, vp, vp, i64, i64, i64, i64,
                                               f32, u64, i32, u64, f32, vp]

@@ -16,6 +16,7 @@ SOURCES = [PKG_DIR / "csrc" / "ob_kernels.hip",
            PKG_DIR / "csrc" / "ob_flash_hd96_bf16.hip",
            PKG_DIR / "csrc" / "ob_flash_bidir_bf16.hip",
            PKG_DIR / "csrc" / "ob_flash_gqa_bf16.hip",
+           PKG_DIR / "csrc" / "ob_flash_seg_bf16.hip",
            PKG_DIR / "csrc" / "ob_blaslt.hip",
            PKG_DIR / "csrc" / "ob_optim.hip",
            PKG_DIR / "csrc" / "ob_dropout.hip",

@@ -38,6 +38,13 @@ class ModelConfig:
     # is qkv_width.  bf16 flash layers at head_dim 128 with attn_pdrop == 0,
     # dense and causal, only.
     n_kv_head: int = 0
+    # Packed sequences: >= 0 is the id of the token that ends a document.  The
+    # token AFTER a separator starts a new document, every block is created
+    # with attn_segments and a query attends the keys of its own document only
+    # (block-diagonal causal attention).  -1: a row is one document.  bf16
+    # flash layers at head_dim 64 or 128 with attn_pdrop == 0, dense and causal,
+    # one K/V head per query head, only.
+    doc_sep_token: int = -1
 
     @property
     def qkv_width(self) -> int:

@@ -240,6 +240,14 @@ static __bf16* shadow(const ob_layer* l, int which) {
 static int64_t* slot_ids(const ob_layer* l, int slot) {
   return l->ids + (int64_t)slot * l->d.max_batch * l->d.seq_len;
 }
+// a segmented BLOCK's document bounds of a slot (ob_layer_plan.h, ids_count):
+// lo [max_batch, S] int32, then hi
+static int32_t* slot_seg_lo(const ob_layer* l, int slot) {
+  return reinterpret_cast<int32_t*>(slot_ids(l, slot));
+}
+static int32_t* slot_seg_hi(const ob_layer* l, int slot) {
+  return slot_seg_lo(l, slot) + (int64_t)l->d.max_batch * l->d.seq_len;
+}
 template <class T>
 struct BlockStash {
   T *x, *ln1, *qkv, *P, *am, *hmid, *ln2, *u, *gact;
@@ -437,6 +445,16 @@ static int layer_create(const ob_layer_desc* d, const ob_dropout_desc* drop,
       hipMalloc(&l->ids, (size_t)pl.ids_count * sizeof(int64_t)) !=
           hipSuccess)
     return ob_fail("create: ids hipMalloc failed");
+  // a segmented layer starts with one document per row in every slot; the
+  // first forward may run on any stream, so wait for the writes here
+  if (ob_plan_seg(*d)) {
+    for (int s = 0; s < d->n_slots; s++)
+      if (ob_flash_seg_bounds_i32(nullptr, slot_seg_lo(l, s),
+                                  slot_seg_hi(l, s), d->max_batch, d->seq_len,
+                                  nullptr))
+        return 1;
+    OB_HIP(hipStreamSynchronize(nullptr));
+  }
   if (pl.shadow_count > 0) {
     if (hipMalloc(&l->shadows, (size_t)pl.shadow_count * sizeof(__bf16)) !=
         hipSuccess)
@@ -487,6 +505,21 @@ extern "C" int ob_layer_set_dropout_tick(ob_layer_t l, uint64_t tick) {
   if (!l) return ob_fail("set_dropout_tick: null layer");
   l->next_tick = tick;
   return 0;
+}
+
+// null doc_start: every row of the slot (max_batch of them) back to one
+// document; else the current batch's rows from the flags
+extern "C" int ob_layer_set_doc_starts(ob_layer_t l, int32_t slot,
+                                       const void* doc_start, void* stream) {
+  if (!l) return ob_fail("set_doc_starts: null layer");
+  if (!ob_plan_seg(l->d))
+    return ob_fail("set_doc_starts: the layer has no attn_segments");
+  if (slot < 0 || slot >= l->d.n_slots)
+    return ob_fail("set_doc_starts: bad slot");
+  return ob_flash_seg_bounds_i32(doc_start, slot_seg_lo(l, slot),
+                                 slot_seg_hi(l, slot),
+                                 doc_start ? l->B : l->d.max_batch,
+                                 l->d.seq_len, stream);
 }
 
 extern "C" int ob_layer_bind(ob_layer_t l, void* params, void* grads) {
@@ -887,7 +920,15 @@ static int block_forward_bf16(ob_layer* l, int slot, const __bf16* in,
   if (l->plan.flash && flash_tr()) {
     // the fused kernel writes O and the per-row LSE (stored where the
     // materialized-P path keeps P)
-    if (ob_plan_gqa(l->d)) {
+    if (ob_plan_seg(l->d)) {
+      // document-masked layer (the plan admits it dense and causal, with
+      // attn_pdrop == 0 only): this slot's bounds
+      if (OB_PROF(OB_PF_FLASH_FWD, stream,
+                  ob_flash_fwd_seg_bf16(s.qkv, slot_seg_lo(l, slot), s.am,
+                                        s.lseP, B, Sq, H, nh,
+                                        1.f / sqrtf((float)hd), stream)))
+        return 1;
+    } else if (ob_plan_gqa(l->d)) {
       // grouped-query layer (the plan admits it at head_dim 128, dense and
       // causal, with attn_pdrop == 0 only)
       if (OB_PROF(OB_PF_FLASH_FWD, stream,
@@ -1144,7 +1185,14 @@ static int block_backward_bf16(ob_layer* l, int slot, const __bf16* dout,
     // also adds the b_qkv grad (column sums of DQKV) from its accumulators
     // (deterministic mode: not asked for; the side-stream colsum below)
     float* const dbq = det ? nullptr : g + bp.b_qkv;
-    if (ob_plan_gqa(l->d)) {
+    if (ob_plan_seg(l->d)) {
+      if (OB_PROF(OB_PF_FLASH_BWD, stream,
+                  ob_flash_bwd_seg_d_bf16(s.qkv, s.am, w.DATT, s.lseP,
+                                          slot_seg_lo(l, slot),
+                                          slot_seg_hi(l, slot), w.D, w.DQKV,
+                                          dbq, B, Sq, H, nh, scale, stream)))
+        return 1;
+    } else if (ob_plan_gqa(l->d)) {
       // the split slab follows D (sized for the layer's max_batch) in
       // WS_FLASH_BWD; split 0: the rule, a fixed-order fold either way
       const int64_t d_floats = (int64_t)l->d.max_batch * nh * Sq;

@@ -69,7 +69,10 @@ struct ob_layer_plan {
   bool side = false;   // needs the side stream
   int64_t v_pad = 0;   // vocab rows of the lm_head shadows, logits and GEMMs
   int64_t st_off[ST_N] = {}, st_len[ST_N] = {}, slot_stride = 0;  // floats
-  int64_t ids_count = 0;  // int64 ids (EMBED) / labels (FINAL), all slots
+  // int64 ids (EMBED) / labels (FINAL), all slots; a segmented BLOCK
+  // (ob_plan_seg): one int64 per token and slot, read as the token's two
+  // int32 document bounds, a slot being [lo [max_batch, S] | hi [max_batch, S]]
+  int64_t ids_count = 0;
   int64_t sh_off[SH_N] = {}, shadow_count = 0;  // bf16 elements
   int64_t ws[WS_N] = {};  // floats needed of each buffer, 0 = not used
   // WS_FLASH_BWD's layout: Q^T, K^T, dO^T (bf16 elements; OB_FLASH_TR=0
@@ -112,6 +115,14 @@ inline int64_t ob_v_pad(int64_t V) { return (V + 255) / 256 * 256; }
 // WS_FLASH_BWD holds D followed by the dK/dV split slab, sized for the
 // largest split ob_flash_gqa_split can return for the description on any CU
 // count.  n_kv_head 0 or n_head is today's layer in every field.
+// A segmented layer (ob_plan_seg: attn_segments set; ob_flash_seg_bf16.hip) is
+// a flash layer at head_dim 64 or 128, with attn_pdrop == 0, no band, causal,
+// one K/V head per query head and flash_tr: those kernels are production-only
+// and have no other variants.  Its plan is the flash plan of the same
+// description plus ids_count, which holds every slot's document bounds.
+inline bool ob_plan_seg(const ob_layer_desc& d) {
+  return d.kind == OB_KIND_BLOCK && d.attn_segments != 0;
+}
 inline bool ob_plan_gqa(const ob_layer_desc& d) {
   return d.kind == OB_KIND_BLOCK && d.n_kv_head != 0 &&
          d.n_kv_head != d.n_head;
@@ -136,6 +147,12 @@ inline bool ob_plan_bidir(const ob_layer_desc& d) {
 }
 inline bool ob_plan_flash(const ob_layer_desc& d, float p_attn,
                           const ob_layer_modes& m) {
+  if (ob_plan_seg(d) &&
+      !(p_attn == 0.f && m.flash_tr && !ob_plan_windowed(d) &&
+        d.attn_window >= 0 && !ob_plan_bidir(d) && !ob_plan_gqa(d) &&
+        d.n_head > 0 &&
+        (d.n_embd == 64 * d.n_head || d.n_embd == 128 * d.n_head)))
+    return false;  // head_dim 128 then also asks for flash_hd128
   if (ob_plan_gqa(d) &&
       !(p_attn == 0.f && !ob_plan_windowed(d) && d.attn_window >= 0 &&
         !ob_plan_bidir(d) && d.n_kv_head > 0 && d.n_head > 0 &&
@@ -187,6 +204,12 @@ inline ob_layer_plan ob_layer_plan_of(const ob_layer_desc& d, float p_resid,
       // the materialized-P route has no band
       if (d.attn_window < 0)
         p.error = "attn_window must be >= 0";
+      else if (ob_plan_seg(d) && !p.flash)
+        p.error =
+            "attn_segments needs a flash layer: bf16, head_dim 64 or 128, "
+            "seq_len % 128 == 0, attn_pdrop == 0, attn_window 0 or >= "
+            "seq_len, attn_bidir == 0, n_kv_head 0 or n_head, and none of "
+            "OB_BF16_FLASH=0, OB_FLASH_TR=0, OB_FLASH_HD128=0 (head_dim 128)";
       else if (ob_plan_gqa(d) && !p.flash)
         p.error =
             "0 < n_kv_head < n_head needs a flash layer: bf16, head_dim 128, "
@@ -205,6 +228,7 @@ inline ob_layer_plan ob_layer_plan_of(const ob_layer_desc& d, float p_resid,
             "attn_pdrop == 0 (> 0 with OB_FLASH_BAND_DROP=1 and not "
             "OB_FLASH_DROP=0), and none of OB_BF16_FLASH=0, OB_FLASH_TR=0, "
             "OB_FLASH_HD128=0 (head_dim 128)";
+      if (ob_plan_seg(d)) p.ids_count = BS * d.n_slots;
       st(ST_X, BSH), st(ST_MEAN1, BS), st(ST_RSTD1, BS), st(ST_LN1, BSH);
       st(ST_QKV, BS * Wq), st(ST_P, p.flash ? Bm * nh * Sq : PSS);
       st(ST_ATTNM, BSH), st(ST_HMID, BSH), st(ST_MEAN2, BS), st(ST_RSTD2, BS);

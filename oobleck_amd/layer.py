@@ -14,7 +14,7 @@ import torch.distributed
 
 from ._ext import ObDropoutDesc, ObLayerDesc, check, get_ext
 from .config import ModelConfig
-from .params import init_layer_params
+from .params import KIND_BLOCK, init_layer_params
 
 
 class _FlatParamHandle:
@@ -52,7 +52,8 @@ class Layer:
                  resid_pdrop: float | None = None,
                  attn_pdrop: float | None = None, dropout_seed: int = 0,
                  attn_window: int | None = None,
-                 attn_causal: bool | None = None):
+                 attn_causal: bool | None = None,
+                 attn_segments: bool | None = None):
         """Dropout: the three probabilities default to the ModelConfig's;
         with all of them 0 the layer is created by ob_layer_create and is
         exactly the dropout-free layer.  Masks are stateless functions of
@@ -63,7 +64,12 @@ class Layer:
         attn_causal: None takes cfg.attn_causal; False makes a BLOCK's
         attention bidirectional (flash-eligible bf16 layers at head_dim 64
         with attn_pdrop == 0 and no window only: anything else fails in the
-        create)."""
+        create).
+        attn_segments: None takes cfg.doc_sep_token >= 0; True makes a
+        BLOCK's attention document-masked, with the documents of a microbatch
+        given to forward_slot (flash-eligible bf16 layers at head_dim 64 or
+        128 with attn_pdrop == 0, dense, causal and not grouped-query only:
+        anything else fails in the create)."""
         self.layer_id = layer_id
         self.cfg = cfg
         self.kind = cfg.layer_kind(layer_id)
@@ -77,6 +83,8 @@ class Layer:
         if attn_causal is None:
             attn_causal = cfg.attn_causal
         self._attn_causal = bool(attn_causal)
+        if attn_segments is None:
+            attn_segments = cfg.doc_sep_token >= 0
         ext = get_ext()
         self._desc = ObLayerDesc(
             kind=self.kind, n_embd=cfg.n_embd, n_head=cfg.n_head,
@@ -84,7 +92,9 @@ class Layer:
             max_batch=max_batch, seq_len=seq_len, n_slots=n_slots,
             dtype=0 if dtype == "f32" else 1, attn_window=self.attn_window,
             attn_bidir=0 if self._attn_causal else 1,
-            n_kv_head=cfg.n_kv_head)
+            n_kv_head=cfg.n_kv_head,
+            attn_segments=1 if attn_segments and self.kind == KIND_BLOCK
+            else 0)
         n = ext.ob_layer_param_count(ctypes.byref(self._desc))
         assert n > 0
         init = init_layer_params(cfg, layer_id, seed, init_style).to(device)
@@ -148,6 +158,12 @@ class Layer:
         == 0, dense and causal, or the create fails."""
         return int(self._desc.n_kv_head)
 
+    @property
+    def attn_segments(self) -> bool:
+        """True: a BLOCK whose attention is document-masked; forward_slot's
+        doc_start sets the documents of a microbatch."""
+        return bool(self._desc.attn_segments)
+
     # -- compute ------------------------------------------------------------
     @property
     def flat_param(self) -> torch.Tensor:
@@ -197,13 +213,29 @@ class Layer:
 
     def forward_slot(self, slot: int, x: torch.Tensor, out: torch.Tensor,
                      labels: torch.Tensor | None = None,
-                     tick: int | None = None) -> None:
+                     tick: int | None = None,
+                     doc_start: torch.Tensor | None = None) -> None:
         """tick: the dropout tick of this forward (every layer of the model
         should see the same tick for the same microbatch).  None continues
         from the layer's own counter, which post-increments per training
-        forward.  The backward of `slot` regenerates this forward's masks."""
+        forward.  The backward of `slot` regenerates this forward's masks.
+        doc_start: on a layer with attn_segments, an int32 [B, S] device
+        tensor, nonzero where a token begins a document (position 0 always
+        does); None makes every row one document.  The backward of `slot`
+        uses the same documents.  Any other layer takes None only."""
         if self._sharded is not None:
             self._unshard()  # pre_forward_hook (layer.py:147-153)
+        if self.attn_segments:
+            if doc_start is not None:
+                assert doc_start.dtype == torch.int32 and doc_start.is_cuda
+                assert doc_start.shape == x.shape[:2]
+            check(get_ext().ob_layer_set_doc_starts(
+                self._h, slot, _ptr(doc_start), _stream_ptr()),
+                f"set_doc_starts layer {self.layer_id}")
+        elif doc_start is not None:
+            raise ValueError(
+                f"layer {self.layer_id} has no attn_segments: doc_start "
+                "must be None")
         if tick is not None and self.has_dropout:
             check(get_ext().ob_layer_set_dropout_tick(self._h, tick),
                   "set_dropout_tick")

@@ -15,7 +15,7 @@ import torch
 import torch.distributed as dist
 
 from .config import ModelConfig, TrainingConfig
-from .params import KIND_EMBED, KIND_FINAL
+from .params import KIND_BLOCK, KIND_EMBED, KIND_FINAL
 from .schedule import (BackwardPass, ForwardPass, LoadMicroBatch,
                        OobleckPipelineSchedule, RecvActivation, RecvGrad,
                        SendActivation, SendGrad)
@@ -99,6 +99,7 @@ class PipelineExecution:
         self._out_bufs: dict[int, torch.Tensor] = {}
         self._loss_bufs: dict[int, torch.Tensor] = {}
         self._din_bufs: dict[int, torch.Tensor] = {}
+        self._doc_bufs: dict[int, torch.Tensor] = {}  # per-slot doc_start
         # single-stage (pp1) GPU overlap: forward of microbatch m+1 runs
         # on its own HIP stream beside backward of microbatch m (the 1F1B
         # schedule at stages=1 alternates F/B).  Slot reuse and the
@@ -219,6 +220,20 @@ class PipelineExecution:
         if self._any_dropout:
             tick = self.dropout_tick(self._mb_fwd)
         self._mb_fwd += 1
+        # packed sequences: the token after a separator starts a document.
+        # labels is a copy of input_ids and reaches every stage, so each
+        # stage derives the same flags; no host sync.  One buffer per slot:
+        # the slot's previous backward is fenced before this forward.
+        seg_kw = {}
+        sep = getattr(self.pipeline.model_cfg, "doc_sep_token", -1)
+        if sep >= 0:
+            ds = self._doc_bufs.get(buffer_id)
+            if ds is None or ds.shape != labels.shape:
+                ds = torch.zeros(labels.shape, dtype=torch.int32,
+                                 device=labels.device)
+                self._doc_bufs[buffer_id] = ds
+            ds[:, 1:] = labels[:, :-1] == sep
+            seg_kw = {"doc_start": ds}
         for i, layer in enumerate(self._layers):
             layer.set_batch(batch)
             if layer.kind == KIND_FINAL:
@@ -242,10 +257,11 @@ class PipelineExecution:
                     out = out[:batch]
                 else:
                     out = self._get_tmp(i % 2, batch)
+                kw = seg_kw if layer.kind == KIND_BLOCK else {}
                 if tick is None:
-                    layer.forward_slot(buffer_id, x, out)
+                    layer.forward_slot(buffer_id, x, out, **kw)
                 else:
-                    layer.forward_slot(buffer_id, x, out, tick=tick)
+                    layer.forward_slot(buffer_id, x, out, tick=tick, **kw)
             x = out
 
         if self.pipeline.is_last_stage():
